@@ -11,7 +11,8 @@ the per-frame pose records to rank 0 (RCCL point-to-point, 432 B/frame, asynchro
 GPU, rendezvous on 127.0.0.1) when it was not already started by a launcher (WORLD_SIZE unset); under a launcher it
 checks that WORLD_SIZE == N.  Fewer visible GPUs than ranks is a hard error, never a silent share.
 
-Prints ONE JSON line (rank 0): metric / value as BASELINE.json on C2, plus
+Prints ONE JSON line (rank 0): metric / value as BASELINE.json on C2, ms_per_step of the --steps timed steps.  A plain
+run does only that: set up, warm up, time the steps, write --dump-outputs, print.  With --full the line also holds
   roofline       the kernel that moves the image bytes in the timed mode (the voting kernel that carries the scan
                  of the next sub-batch): algorithmic bytes (rows*cols per frame scanned) / HIP-event time of its
                  launches inside the timed region; roofline_isolated = k1a_scan alone
@@ -22,7 +23,9 @@ and — at N = 1, after the headline leg and outside its timed region, each with
   clutter        C2 with 4 / 16 distractor spots, 0.05 % salt noise, a saturated 64x64 patch
   tracked        the stateful estimator: one stream (latency), 8 and 64 streams in lock step (configs[4] on one GPU)
   latency_ms_one_frame   one brute-force frame, host memory in / record out
-and — at N > 1 — ranks_seen, per_rank_fps and shard_parity (a sample of EVERY rank's shard checked on rank 0).
+and — at N > 1 — ranks_seen, per_rank_fps and (--full) shard_parity (a sample of EVERY rank's shard checked on rank 0).
+--dump-outputs DIR writes the pose records of the last timed step (rank 0: every rank's, as gathered) to DIR/<field>.npy
+in float64, a fixed sample of DUMP_MAX_FRAMES frames when the step has more (DIR/frame_index.npy says which).
 Exit codes: 3 = a mismatch that is not a witnessed instability of the reference algorithm, 4 = a fraction above 1.
 Prose about what each field means lives in DESIGN.md section 4, not in the line.
 """
@@ -49,6 +52,7 @@ PMC_FILES = ("round6_pmc.json", "round5_pmc.json", "round4_pmc.json", "round3_pm
 SPEC_CLOCK_GHZ = 2.4
 VALU_ISSUE_PEAK = 1024 * SPEC_CLOCK_GHZ / 4.0  # G wave-instructions/s
 SAMPLE_PER_RANK = 64  # frames of every rank's shard that rank 0 checks against the oracle at N > 1
+DUMP_MAX_FRAMES = 65536  # --dump-outputs: 57 float64 per frame (record fields + frame index) -> at most 30 MB
 
 
 def effective_cores():
@@ -81,6 +85,19 @@ def records_checksum(rec):
     for k in ("status", "n_det", "n_corr", "T"):
         h.update(np.ascontiguousarray(rec[k]).tobytes())
     return h.hexdigest()[:16]
+
+
+def dump_records(out_dir, rec):
+    """--dump-outputs: every field of the pose records as DIR/<field>.npy (float64, one row per frame) and the frames
+    they belong to as DIR/frame_index.npy; more than DUMP_MAX_FRAMES frames are represented by a fixed, seeded sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(rec)
+    idx = np.arange(n)
+    if n > DUMP_MAX_FRAMES:
+        idx = np.sort(np.random.default_rng(20261016).choice(n, DUMP_MAX_FRAMES, replace=False))
+    np.save(os.path.join(out_dir, "frame_index.npy"), idx.astype(np.float64))
+    for name in rec.dtype.names:
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(rec[name][idx], dtype=np.float64))
 
 
 def plumbing_only(args, rank, world):
@@ -272,10 +289,22 @@ def load_pmc(mpe):
     return {}, None, None
 
 
+def fractions_above_one(out, config):
+    """True (and said on stderr) when a fraction of a peak in the record exceeds 1: the measurement is broken."""
+    bad_frac = [k for k in ("roofline", "roofline_isolated") if out.get(k) and (out[k].get("frac") or 0) > 1.0]
+    if out["step_hbm"]["frac_of_spec"] > 1.0:
+        bad_frac.append("step_hbm")
+    if bad_frac:
+        sys.stderr.write("bench.py: %s of %s reports more than its peak — the measurement is broken\n"
+                         % (", ".join(bad_frac), config))
+    return bool(bad_frac)
+
+
 # ---- one configuration through the streaming entry -------------------------------------------------------------------
-def run_config(args, ctx, light=False):
+def run_config(args, ctx, light=False, full=True, dump_dir=None):
     """-> (record for the JSON line or None on ranks > 0, parity_failed, impossible).  `light`: a secondary leg — no
-    false-hint leg, no host-streamed leg, no isolated-kernel pass."""
+    false-hint leg, no host-streamed leg, no isolated-kernel pass.  `full` False: the timed steps alone — nothing after
+    them but the records written to `dump_dir` (if given) and the line's headline fields."""
     import torch
     import rpg_monocular_pose_estimator_amd as mpe
     from rpg_monocular_pose_estimator_amd import synth, parallel
@@ -390,8 +419,10 @@ def run_config(args, ctx, light=False):
     # per-step durations as well (median reported next to the mean the bracket yields)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     # the dominant kernel is timed INSIDE the timed region: a pair of HIP events around every voting launch that
-    # carries a scan, on the stream it is launched on, nothing else recorded (option "vote_events")
-    if args.vote_events:
+    # carries a scan, on the stream it is launched on, nothing else recorded (option "vote_events"; only the roofline of
+    # a full run reads them)
+    vote_events = full and args.vote_events
+    if vote_events:
         h.set_option("vote_events", args.steps)
     t0 = time.perf_counter()
     marks[0].record(work_stream)
@@ -410,7 +441,7 @@ def run_config(args, ctx, light=False):
         timed_rec = parallel.records_from_bytes(pipe.local(last_k))
     gathered_last = parallel.records_from_bytes(pipe.gathered(last_k)) if (multi and rank == 0) else None
     vote_in_region_ms, vote_in_region_n, vote_by_slot = None, 0, None
-    if args.vote_events:
+    if vote_events:
         vote_in_region_n = h.get_option("vote_launches")
         if vote_in_region_n > 0:
             vote_in_region_ms = h.get_option("vote_launch_ns_mean") * 1e-6
@@ -430,6 +461,56 @@ def run_config(args, ctx, light=False):
     fix_items = h.get_option("vote_fixup_items")
     fix_overflow = h.get_option("vote_fixup_overflow")
     relost = h.get_option("vote_relost_frames")
+
+    out = None
+    impossible = False
+    if rank == 0:
+        n_pose = int((timed_rec["status"] == 0).sum())
+        out = {
+            # BASELINE.json's metric string for the configuration it is quoted on (C2); the other legs say what they are
+            "metric": (METRIC if (args.config == "C2" and args.clutter is None) else
+                       "frames/sec at %dx%d, %d LEDs / %d spots%s, brute-force init (not the headline)"
+                       % (cols, rows, len(markers), len(markers) + cfg["n_distractors"],
+                          "" if args.clutter is None else ", " + CLUTTER[args.clutter])),
+            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "ms_per_step_median": float(np.median(step_ms)),
+            "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "%s: %dx%d synthetic frames, %d LEDs, %d distractors%s, brute-force P3P init every "
+                                   "frame, demo.launch parameters%s"
+                                   % (args.config, cols, rows, len(markers), cfg["n_distractors"],
+                                      "" if args.clutter is None else " + " + CLUTTER[args.clutter],
+                                      "" if args.back_tol is None else
+                                      " except back_projection_pixel_tolerance = %g" % args.back_tol),
+                       "frames_per_gpu_per_step": B, "frames_resident_in_hbm": True,
+                       "side_streams_concurrent": h.get_option("streams_concurrent"),
+                       "scan_split_pct": h.get_option("scan_split_pct"), "side_scan_blocks": h.get_option("side_scan_blocks"),
+                       "entry": ("mpe_estimate_batch_device_submit / _collect" if streaming else "mpe_estimate_batch_device"),
+                       "records_to_host": bool(args.records_to_host),
+                       "parallelism": "frames sharded over %d GPU(s), pose records gathered to rank 0" % world},
+            "poses_found_frac": n_pose / B,
+            "vote_arith": {"option": args.vote_arith,
+                           "hypotheses_re_evaluated_strictly_per_step": fix_items / max(1, args.steps + args.warmup),
+                           "suspect_list_full_events": fix_overflow, "frames_voted_again": relost},
+            # every pixel of the batch is read once per step: the whole-step HBM rate against the 8 TB/s spec
+            "step_hbm": {"bytes_per_step": B * rows * cols, "achieved_GBps": world * B * rows * cols / (dt / args.steps) / 1e9,
+                         "frac_of_spec": B * rows * cols / (dt / args.steps) / 1e9 / 8000.0},
+        }
+        if multi:
+            out["ranks_seen"] = ranks_seen
+            out["per_rank_fps"] = per_rank_fps
+            if world == 1:
+                out["forced_process_group"] = ("one-rank nccl (RCCL) group: record gather (dist.gather, asynchronous, on "
+                                               "the consumer stream), barrier, all_reduce, all_gather executed on this GPU")
+        if dump_dir:
+            dump_records(dump_dir, gathered_last if multi else timed_rec)
+    if not full:
+        if rank == 0:
+            impossible = fractions_above_one(out, args.config)
+        h.close()
+        del frames, pipe, results, host_rec
+        torch.cuda.empty_cache()
+        return out, False, impossible
 
     # ---- the same steps with a next-batch announcement that does NOT come true (the timed region above is the best
     #      case: every hint is right).  The announced pointer is another view of the same frames, so the submission
@@ -638,44 +719,10 @@ def run_config(args, ctx, light=False):
         host_leg = {"fps": nh / dt_h, "GBps": nh * rows * cols / dt_h / 1e9, "frames_per_call": nh}
         pin.close()
 
-    out = None
     parity_failed = False
-    impossible = False
     if rank == 0:
-        n_pose = int((timed_rec["status"] == 0).sum())
-        out = {
-            # BASELINE.json's metric string for the configuration it is quoted on (C2); the other legs say what they are
-            "metric": (METRIC if (args.config == "C2" and args.clutter is None) else
-                       "frames/sec at %dx%d, %d LEDs / %d spots%s, brute-force init (not the headline)"
-                       % (cols, rows, len(markers), len(markers) + cfg["n_distractors"],
-                          "" if args.clutter is None else ", " + CLUTTER[args.clutter])),
-            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "ms_per_step_median": float(np.median(step_ms)),
-            "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "%s: %dx%d synthetic frames, %d LEDs, %d distractors%s, brute-force P3P init every "
-                                   "frame, demo.launch parameters%s"
-                                   % (args.config, cols, rows, len(markers), cfg["n_distractors"],
-                                      "" if args.clutter is None else " + " + CLUTTER[args.clutter],
-                                      "" if args.back_tol is None else
-                                      " except back_projection_pixel_tolerance = %g" % args.back_tol),
-                       "frames_per_gpu_per_step": B, "frames_resident_in_hbm": True,
-                       "schedule": schedule, "side_streams_concurrent": h.get_option("streams_concurrent"),
-                       "scan_split_pct": h.get_option("scan_split_pct"), "side_scan_blocks": h.get_option("side_scan_blocks"),
-                       "entry": ("mpe_estimate_batch_device_submit / _collect" if streaming else "mpe_estimate_batch_device"),
-                       "records_to_host": bool(args.records_to_host),
-                       "parallelism": "frames sharded over %d GPU(s), pose records gathered to rank 0" % world},
-            "poses_found_frac": n_pose / B,
-            "blob_tier_overflow": overflow,
-            "vote_arith": {"option": args.vote_arith,
-                           "hypotheses_re_evaluated_strictly_per_step": fix_items / max(1, args.steps + args.warmup),
-                           "suspect_list_full_events": fix_overflow, "frames_voted_again": relost},
-            # every pixel of the batch is read once per step: the whole-step HBM rate against the 8 TB/s spec
-            "step_hbm": {"bytes_per_step": B * rows * cols, "achieved_GBps": world * B * rows * cols / (dt / args.steps) / 1e9,
-                         "frac_of_spec": B * rows * cols / (dt / args.steps) / 1e9 / 8000.0},
-            "kernel_ms": kavg,
-            "roofline": roofline,
-        }
+        out["config"]["schedule"] = schedule
+        out.update({"blob_tier_overflow": overflow, "kernel_ms": kavg, "roofline": roofline})
         if false_hint is not None:
             out["false_hint_leg"] = false_hint
         if kiso is not None:
@@ -703,12 +750,6 @@ def run_config(args, ctx, light=False):
         if host_leg is not None:
             out["host_streamed_fps"] = host_leg["fps"]
             out["host_streamed"] = host_leg
-        if multi:
-            out["ranks_seen"] = ranks_seen
-            out["per_rank_fps"] = per_rank_fps
-            if world == 1:
-                out["forced_process_group"] = ("one-rank nccl (RCCL) group: record gather (dist.gather, asynchronous, on "
-                                               "the consumer stream), barrier, all_reduce, all_gather executed on this GPU")
         # ---- CPU baseline + parity on a bounded sample (oracle = test infrastructure / checker) ----
         if not args.no_cpu and args.cpu_sample > 0:
             import oracle
@@ -745,13 +786,7 @@ def run_config(args, ctx, light=False):
                                   "status_mismatches": blk["status_mismatches"], "pos_max_m": blk["pos_max_m"],
                                   "mismatches_unexplained": blk["mismatches_unexplained"]})
                 out["shard_parity"] = shard
-        bad_frac = [k for k in ("roofline", "roofline_isolated") if out.get(k) and (out[k].get("frac") or 0) > 1.0]
-        if out["step_hbm"]["frac_of_spec"] > 1.0:
-            bad_frac.append("step_hbm")
-        if bad_frac:
-            sys.stderr.write("bench.py: %s of %s reports more than its peak — the measurement is broken\n"
-                             % (", ".join(bad_frac), args.config))
-            impossible = True
+        impossible = fractions_above_one(out, args.config)
     h.close()
     del frames, pipe, results, host_rec
     torch.cuda.empty_cache()
@@ -912,6 +947,14 @@ def main():
     ap.add_argument("--config", default="C2")
     ap.add_argument("--clutter", default=None, choices=sorted(CLUTTER), help="C2 + clutter: " + ", ".join(
         "%s = %s" % kv for kv in sorted(CLUTTER.items())))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the timed steps: per-kernel times and rooflines, the false-hint, isolated-kernel "
+                         "and host-streamed legs, CPU baseline and parity against the oracle, and (C2 at the default "
+                         "batch, one GPU) the other configs, the clutter legs, the tracked streams and the one-frame "
+                         "latency.  The options below that shape those parts act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the pose records of the last timed step to DIR/<field>.npy (float64; a fixed sample of "
+                         "%d frames when the step has more, DIR/frame_index.npy says which)" % DUMP_MAX_FRAMES)
     ap.add_argument("--cpu-sample", type=int, default=16384, help="frames timed on the CPU oracle (0 = skip)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
@@ -969,6 +1012,8 @@ def main():
                     help="no GPU work: the launch / shard / pose-gather / timing plumbing of the N-rank bench on CPU "
                          "(gloo), with synthetic records instead of kernels; used by the CPU test-suite")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     headline = args.config == "C2" and args.clutter is None and args.frames <= 0
     if args.frames <= 0:
         args.frames = {"C2": 262144, "C1": 65536, "C3": 65536, "C4": 16384}.get(args.config, 16384)
@@ -1019,9 +1064,9 @@ def main():
            "force_pg": args.force_process_group}
 
     t_start = time.perf_counter()
-    out, parity_failed, impossible = run_config(args, ctx)
+    out, parity_failed, impossible = run_config(args, ctx, full=args.full, dump_dir=args.dump_outputs)
     legs_failed = []
-    if rank == 0 and world == 1 and headline and not args.headline_only and not args.force_process_group:
+    if args.full and rank == 0 and world == 1 and headline and not args.headline_only and not args.force_process_group:
         # ---- every other BASELINE config, the clutter curve, the tracked streams, one frame: after the headline leg,
         #      outside its timed region, each with its own roofline and parity sample against the oracle
         out["headline_leg_s"] = round(time.perf_counter() - t_start, 1)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collection with the committed binary (round 6 on; parametrised by the round number): the GPU suite, every profiler
-# pass the bench line and DESIGN.md quote (tied to the sources by source_fingerprint), the default bench line (all
+# pass the bench line and DESIGN.md quote (tied to the sources by source_fingerprint), the full bench line (all
 # configs, clutter, tracked streams), the parity soaks.
 #   gpurun --timeout 2400 -- 'bash profiles/collect.sh 6'; then python profiles/install.py 6
 # Counter passes: `--kernel-trace` + `--pmc` only, FETCH_SIZE / WRITE_SIZE / SQ in separate runs, mpe:: kernels only.
@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $R && timeout 600 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc $?" >> $O/pytest_gpu.log
 cd /tmp
 python -c "import sys; sys.path.insert(0, '$R'); import rpg_monocular_pose_estimator_amd as m; print(m.source_fingerprint())" > $O/source_fingerprint.txt
-Q="--no-cpu --no-host-leg --no-false-hint-leg --headline-only --no-isolated"
+Q="--full --no-cpu --no-host-leg --no-false-hint-leg --headline-only --no-isolated"
 SQ="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVES GRBM_GUI_ACTIVE"
 INC='--kernel-include-regex mpe::'
 pmc() {  # name, counters, bench args...
@@ -59,10 +59,10 @@ find $O -name "*kernel_trace.csv" -delete; find $O -name "*agent_info.csv" -dele
 #      gpurun_out/ and produces the same file): the bench line below then carries traffic / VALU fractions from
 #      counters of the binary it times (source_fingerprint match True)
 python $R/profiles/install.py $ROUND > $O/install_on_box.log 2>&1
-# ---- the default bench line, as the driver runs it
-( time timeout 400 python $R/bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" >> $O/bench.err ) 2>> $O/bench.err
+# ---- the full bench line (--full: every config, clutter, tracked streams)
+( time timeout 400 python $R/bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" >> $O/bench.err ) 2>> $O/bench.err
 # same box A/B: headline alone; default (vote_arith 3) vs exact powers (1) vs the fast arithmetic alone (2)
-QB="--no-cpu --no-host-leg --no-false-hint-leg --headline-only"
+QB="--full --no-cpu --no-host-leg --no-false-hint-leg --headline-only"
 timeout 200 python $R/bench.py $QB --steps 20 --warmup 5 2>/dev/null > $O/bench_headline_only.json
 timeout 200 python $R/bench.py $QB --steps 20 --warmup 5 --vote-arith 1 2>/dev/null > $O/bench_arith1.json
 timeout 200 python $R/bench.py $QB --steps 20 --warmup 5 --vote-arith 2 2>/dev/null > $O/bench_arith2.json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Experiment (round 5): stream priority of the tail stream (fix-up + validate + refine) and of the side-scan stream.
 O=gpurun_out/r5e; mkdir -p $O
-Q="--no-cpu --no-host-leg --no-false-hint-leg --headline-only --steps 15 --warmup 4"
+Q="--full --no-cpu --no-host-leg --no-false-hint-leg --headline-only --steps 15 --warmup 4"
 run() {
   python bench.py $Q "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernel_ms']['per_sub_batch'][1:7]; print('$*', round(d['ms_per_step'],3), round(d['ms_per_step_median'],3), 'blobs', round(sum(x['blobs'] for x in k)/6,3), 'vote', round(sum(x['vote'] for x in k)/6,3), 'tail', round(sum(x['tail'] for x in k)/6,3))" >> $O/out.txt
 }

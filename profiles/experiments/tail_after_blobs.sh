@@ -2,7 +2,7 @@
 # Experiment (round 5): the tail chain of sub-batch s held back until blobs(s + 1) is done (option tail_after_blobs),
 # with k2_vote_relost as one-wave blocks; interleaved A/B on one box + the GPU suite on the new default.
 O=gpurun_out/r5o; mkdir -p $O
-Q="--no-cpu --no-host-leg --no-false-hint-leg --headline-only --steps 20 --warmup 5"
+Q="--full --no-cpu --no-host-leg --no-false-hint-leg --headline-only --steps 20 --warmup 5"
 run() {
   python bench.py $Q "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['roofline']['timed_region_by_slot']; k=d['kernel_ms']['per_sub_batch'][1:7]; print('$*', round(d['ms_per_step'],3), round(d['ms_per_step_median'],3), 'gaps', round(sum(x['gap_before_ms'] for x in s)/8,3), 'launch', round(sum(x['launch_ms'] for x in s)/8,3), 'tail', round(sum(x['tail'] for x in k)/6,3))" >> $O/out.txt
 }

@@ -4,7 +4,7 @@
 O=gpurun_out/r5q; mkdir -p $O
 run() {
   local lib=$1; shift
-  MPE_LIB=$lib python bench.py --no-host-leg --no-false-hint-leg --headline-only --cpu-sample 256 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$(basename $lib) $*', round(d['value']), round(d['ms_per_step'],3), 'vote', round(d['kernel_ms']['vote'],3), 'tail', round(d['kernel_ms']['tail'],3), 'parity', d['parity']['status_mismatches'], d['parity']['mismatches_unexplained'], 'fix', round(d['vote_arith']['hypotheses_re_evaluated_strictly_per_step']), d['vote_arith']['frames_voted_again'])" >> $O/out.txt
+  MPE_LIB=$lib python bench.py --full --no-host-leg --no-false-hint-leg --headline-only --cpu-sample 256 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$(basename $lib) $*', round(d['value']), round(d['ms_per_step'],3), 'vote', round(d['kernel_ms']['vote'],3), 'tail', round(d['kernel_ms']['tail'],3), 'parity', d['parity']['status_mismatches'], d['parity']['mismatches_unexplained'], 'fix', round(d['vote_arith']['hypotheses_re_evaluated_strictly_per_step']), d['vote_arith']['frames_voted_again'])" >> $O/out.txt
 }
 B=rpg_monocular_pose_estimator_amd/libmpe_hip.so
 V=build_variants/libmpe_hip_vq60.so

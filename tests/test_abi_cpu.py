@@ -547,9 +547,10 @@ def test_kernel_sources_read_as_one_text():
     assert len(mpe.source_fingerprint()) == 16
 
 
-def test_bench_line_helpers():
+def test_bench_line_helpers(tmp_path):
     """bench.py's pure helpers: floats slimmed to 6 significant digits (NaN / inf -> null: the line must stay JSON),
-    numpy scalars unwrapped, the order-sensitive record digest."""
+    numpy scalars unwrapped, the order-sensitive record digest, the --dump-outputs writer (float64 fields, a fixed
+    sample of a batch above its cap, at most 64 MB)."""
     import json
     sys.path.insert(0, ROOT)
     import bench
@@ -566,6 +567,20 @@ def test_bench_line_helpers():
     rec2 = rec.copy()
     rec2["T"][5, 7] += 1e-12
     assert a != bench.records_checksum(rec2)
+    big = np.zeros(bench.DUMP_MAX_FRAMES + 1000, mpe.RESULT_DTYPE)
+    big["n_det"] = np.arange(len(big))
+    for d in ("a", "b"):
+        bench.dump_records(str(tmp_path / d), big)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["frame_index.npy"] + [n + ".npy" for n in mpe.RESULT_DTYPE.names])
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    idx = np.load(tmp_path / "a" / "frame_index.npy")
+    assert len(idx) == bench.DUMP_MAX_FRAMES and np.all(np.diff(idx) > 0)
+    for n in names:
+        x = np.load(tmp_path / "a" / n)
+        assert x.dtype == np.float64 and len(x) == bench.DUMP_MAX_FRAMES
+        assert np.array_equal(x, np.load(tmp_path / "b" / n))
+    assert np.array_equal(np.load(tmp_path / "a" / "n_det.npy"), idx)
 
 
 def test_bench_streams_plumbing_two_ranks():

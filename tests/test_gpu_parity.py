@@ -1421,8 +1421,8 @@ def test_bench_entry_on_the_gpu_box():
     import torch
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "32768", "--steps", "3", "--warmup", "1",
-                          "--cpu-sample", "256"], capture_output=True, text=True, env=env, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--frames", "32768", "--steps", "3",
+                          "--warmup", "1", "--cpu-sample", "256"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-1500:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1436,6 +1436,39 @@ def test_bench_entry_on_the_gpu_box():
         few = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1"],
                              capture_output=True, text=True, env=env, timeout=300)
         assert few.returncode != 0 and "GPU(s) are visible" in few.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench run times its steps and prints the headline fields alone (what --full adds is absent);
+    --dump-outputs writes the pose records of the last timed step as float64 arrays, identical from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / ("run%d" % i))
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "8192", "--steps", "2",
+                              "--warmup", "1", "--dump-outputs", d], capture_output=True, text=True, env=env, timeout=300)
+        assert out.returncode == 0, out.stderr[-1500:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["n_gpus"] == 1
+        assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["unit"] == "frames/s" and rec["dtype"] == "f64"
+        assert rec["higher_is_better"] is True
+        assert not {"roofline", "kernel_ms", "parity", "cpu_baseline", "other_configs"} & set(rec), sorted(rec)
+        files = sorted(os.listdir(d))
+        assert files == ["T.npy", "cov.npy", "frame_index.npy", "gn_iterations.npy", "n_corr.npy", "n_det.npy",
+                         "status.npy"]
+        arr = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype == np.float64 and len(a) == 8192 for a in arr.values())
+        assert abs(float((arr["status.npy"] == 0).mean()) - rec["poses_found_frac"]) < 1e-6
+        dumps.append(arr)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f], equal_nan=True) for f in dumps[0])
 
 
 @pytest.mark.gpu
@@ -1487,7 +1520,7 @@ def test_bench_collectives_on_a_one_rank_rccl_group():
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-process-group", "--frames", "65536",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--force-process-group", "--frames", "65536",
                         "--steps", "3", "--warmup", "1", "--no-host-leg", "--no-false-hint-leg", "--headline-only",
                         "--no-isolated"], capture_output=True, text=True, timeout=400, env=env, cwd=root)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$1; REPS=$2; LIBS=$3; shift 3
 mkdir -p $O
 cd $R
-QB="--no-cpu --no-host-leg --no-false-hint-leg --headline-only"
+QB="--full --no-cpu --no-host-leg --no-false-hint-leg --headline-only"
 for rep in $(seq 1 $REPS); do
   for c in "$@"; do
     for L in $LIBS; do

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 name=$1; shift
 O=$R/gpurun_out/$name; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o s -- python $R/bench.py --no-cpu --no-host-leg \
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o s -- python $R/bench.py --full --no-cpu --no-host-leg \
   --no-false-hint-leg --headline-only "$@" > $O/run.log 2>&1
 python - "$O" <<PY
 import csv, glob, sys

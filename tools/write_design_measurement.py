@@ -27,7 +27,7 @@ sec4 = '''`python bench.py` = C2 (`BASELINE.json configs[1]`): 262 144 distinct 
 records into pinned host memory on a consumer stream.  All numbers: `profiles/round6_*`, one collection with the
 committed binary (`profiles/collect.sh 6` → `install.py 6`; the counter file carries the fingerprint of the kernel + host
 sources, `%s`, and the bench line says whether it matches: %s).  This text is generated from those files
-(`tools/write_design_measurement.py`).
+(`tools/write_design_measurement.py`).  A plain `python bench.py` prints the headline fields alone; the rest comes with `--full`.
 * **value: %s frames/s** (%.2f ms per step, median %.2f; `round6_bench.json`)%s.  Boxes — and runs on one box — differ by
   ± 3 %% (17.3 – 18.4 ms over the round's boxes and A/B runs; runs on ONE box fall into two modes, ~17.4 and ~18.3 ms), so
   the round's claims are interleaved same-box A/Bs: `vote_arith` 3 / 1 / 2 17.82 / 17.83 / 17.82 ms in the mean of five runs each

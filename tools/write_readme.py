@@ -28,7 +28,7 @@ pose covariance — behind a C ABI (`include/mpe.h`) and a source-compatible `Po
 * `bench.py` (headline: batched brute force), `bench_streams.py` (independent tracked camera streams), `__graft_entry__.py`, `profiles/`, `tools/` — measurement
 * `DESIGN.md` (path, kernels, rooflines), `INTEGRATION.md` (how to bind it), `SURVEY.md` (scope contract)
 ''')
-print('''On one MI355X (round 6, `profiles/round6_*`; every figure below is in the default `python bench.py` line, i.e. under
+print('''On one MI355X (round 6, `profiles/round6_*`; every figure below is in the `python bench.py --full` line, i.e. under
 the driver's clock, with its own roofline and oracle parity sample, and as a flat key of `config`): **%s frames/s** at
 752×480 / 5 LEDs with brute-force initialisation on every frame (%.2f ms per 262 144 frames in the collection's default
 line; 17.05 – 17.9 ms over the round's boxes; target 50 k fps; rounds 5 … 1: 14.6 M, 14.7 M, 13.9 M, 13.3 M, 10.0 M),
@@ -59,8 +59,10 @@ print('''```
 python -c "import __graft_entry__ as g; g.build()"     # hipcc + g++, no GPU needed
 python -m pytest tests -q -m "not gpu"                 # CPU suite
 python -m pytest tests -q -m gpu                       # on an MI355X
-python bench.py                                        # one JSON line: headline + every config, clutter, tracked streams (24 s)
-python bench.py --headline-only                        # the C2 leg alone
+python bench.py                                        # one JSON line: the C2 headline alone (timed steps, nothing else)
+python bench.py --dump-outputs DIR                     # + the pose records of the last timed step as DIR/<field>.npy
+python bench.py --full                                 # + rooflines, oracle parity, CPU baseline, every config, clutter, tracked streams (24 s)
+python bench.py --full --headline-only                 # the C2 leg with its roofline and parity
 python bench.py --gpus 8                               # launches its own 8 ranks (one per GPU, RCCL pose gather)
 python bench_streams.py --streams 8                    # stateful estimator, 8 camera streams, one thread each
 python bench_streams.py --streams 64 --lockstep        # 64 streams in lock step: one launch per time step
