@@ -313,7 +313,8 @@ int mpe_track_step(mpe_handle* h, const uint8_t* img, int rows, int cols, size_t
  * a uniform slot array (zero beyond the ROI; the blob kernels read the window size / origin per slot, so image
  * borders and centroid offsets are those of the stand-alone clone of led_detector.cpp:44), one image scan, one
  * blob extraction and one validate / refine kernel pair run over the N slots, one copy returns N records.
- * All streams share rows / cols / stride, camera, marker set and parameters.  predicted_px == NULL for an
+ * All streams share rows / cols / stride, camera, marker set and parameters (streams of different set-ups:
+ * mpe_track_step_batch_setups below).  predicted_px == NULL for an
  * item = detection only (out[i].status = 1).  Group items of very different ROI size into separate calls:
  * the slot is as large as the largest ROI of the call.  dets_out n, corr_out n x 2*MPE_MAX_MARKERS, out n. */
 typedef struct mpe_track_item {
@@ -336,6 +337,30 @@ int mpe_track_step_batch_collect(mpe_handle* h, mpe_detections* dets_out, uint32
  * records that were never written).  _cancel abandons the submission in flight, if any: it waits for the device and
  * frees the handle for the next _submit / mpe_track_step (used on error paths that drive several handles). */
 int mpe_track_step_batch_cancel(mpe_handle* h);
+/* Lock-step batches whose streams differ in camera, marker set and parameters: every physical camera of a rig has its own
+ * K / D (the reference: one PoseEstimator per camera, each with its own calibration and object,
+ * pose_estimator.h:63,82-83, filled per node from that camera's camera_info, monocular_pose_estimator.cpp:103-120).
+ * A set-up is one such camera + marker set + parameter set (n_markers 1 .. MPE_MAX_MARKERS); item i runs with
+ * setups[item_setup[i]].  All items share rows / cols / stride.  Each item's records are byte-identical to those of
+ * mpe_track_step_batch over the items of its set-up alone.  Records come back in the caller's item order; the fused time
+ * step stays ONE launch for the whole submission (set-ups of more than 8 markers, track_fused 0 and slots that overflow
+ * the small blob tier run per set-up through the chain of kernels).  mpe_track_step_batch_collect / _cancel serve this
+ * submit too.  MPE_ERR_ARG before any device work on a null pointer, a set-up index out of range, n_markers above
+ * MPE_MAX_MARKERS or a ROI outside the image. */
+typedef struct mpe_track_setup {
+  const mpe_params* p;
+  const double* K;            /* 3x3 row-major */
+  const double* D;            /* nD distortion coefficients (may be NULL when nD == 0) */
+  int nD;
+  const double* markers_xyz;  /* n_markers x 3 */
+  int n_markers;
+} mpe_track_setup;
+int mpe_track_step_batch_setups(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows,
+                                int cols, size_t stride_bytes, const mpe_track_setup* setups, int n_setups,
+                                mpe_detections* dets_out, uint32_t* corr_out, mpe_result* out);
+int mpe_track_step_batch_setups_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                                       int rows, int cols, size_t stride_bytes, const mpe_track_setup* setups,
+                                       int n_setups);
 /* mpe_solve_bruteforce for N detection sets in one submission (the re-initialisations of a lock-step batch):
  * det_xy n x MPE_MAX_DETECTIONS x 2 (n_det[i] valid rows); hist (optional) n x MPE_MAX_DETECTIONS x
  * MPE_MAX_MARKERS, corr (optional) n x 2*MPE_MAX_MARKERS. */
@@ -392,6 +417,22 @@ int mpe_tracker_run_sequences_batch_threads(mpe_tracker* const* trackers, int n,
                                             int n_frames, int rows, int cols, size_t stride_bytes,
                                             size_t frame_stride_bytes, const double* times, mpe_result* out, int* info,
                                             int n_threads);
+
+/* mpe_tracker_estimate_batch for trackers that may differ in camera, marker set and parameters (one PoseEstimator per
+ * camera: pose_estimator.h:63,82-83, monocular_pose_estimator.cpp:103-120).  The trackers must be distinct and on the
+ * SAME handle (else MPE_ERR_ARG before any device work).  The ROI / whole-image detections of a time step go through
+ * mpe_track_step_batch_setups — in steady state ONE device submission and one launch for all N streams —, the
+ * re-initialisations through one mpe_solve_bruteforce_batch per set-up that has any.  Results are identical to calling
+ * mpe_tracker_estimate per stream, and to mpe_tracker_estimate_batch over each set-up's trackers alone. */
+int mpe_tracker_estimate_batch_mixed(mpe_tracker* const* trackers, int n, const uint8_t* const* imgs, int rows, int cols,
+                                     size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated);
+/* mpe_tracker_run_sequences_batch_threads with groups formed by handle alone: each handle's trackers form one lock-step
+ * group that may mix cameras, marker sets and parameters (as mpe_tracker_estimate_batch_mixed).  Same arguments, same
+ * records as running each set-up's trackers as a uniform group. */
+int mpe_tracker_run_sequences_batch_mixed_threads(mpe_tracker* const* trackers, int n, const uint8_t* const* frames,
+                                                  int n_frames, int rows, int cols, size_t stride_bytes,
+                                                  size_t frame_stride_bytes, const double* times, mpe_result* out,
+                                                  int* info, int n_threads);
 
 /* The estimator's private state (pose_estimator.h:56-62, 74-79), for callers that drive the public
  * step methods of the class (predictPose, findCorrespondences, ... — see compat/) between calls of
@@ -504,6 +545,11 @@ int mpe_set_option(mpe_handle* h, const char* name, int value);
  *   "vote_launch_ns_mean" / "vote_launches" (synchronises the handle's stream); set 0 to release the events.
  * set "track_profile" = 1 starts / resets host-side timers inside mpe_track_step; get "track_ns_pack",
  *   "track_ns_enqueue", "track_ns_wait" (mean ns per step), "track_steps".
+ * get "track_batch_submits", "track_batch_chains", "track_batch_reruns": device submissions of the lock-step batch
+ *   entries (mpe_track_step_batch[_setups][_submit], and the tracker entries on top of them), set-ups of a submission
+ *   that ran through the chain of kernels instead of the one fused launch (track_fused 0, more than 8 markers), and
+ *   set-ups repeated through that chain by _collect because a slot overflowed the small blob tier; since the handle was
+ *   made.
  * get "overflow_frames", "overflow_general", "overflow_why_1" .. "overflow_why_6": frames of the last pipelined batch
  *   that the first blob tier handed on, in all / to the general tier / by the capacity exceeded (bright segments,
  *   bands, islands, pixel pool, bitmap pool, blobs kept); synchronises.

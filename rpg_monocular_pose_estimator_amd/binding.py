@@ -194,6 +194,8 @@ def load_library():
                                                     dp, C.c_void_p, C.c_void_p]
     lib.mpe_tracker_run_sequences_batch_threads.argtypes = [hp, C.c_int, hp, C.c_int, C.c_int, C.c_int, C.c_size_t,
                                                             C.c_size_t, dp, C.c_void_p, C.c_void_p, C.c_int]
+    lib.mpe_tracker_estimate_batch_mixed.argtypes = lib.mpe_tracker_estimate_batch.argtypes
+    lib.mpe_tracker_run_sequences_batch_mixed_threads.argtypes = lib.mpe_tracker_run_sequences_batch_threads.argtypes
     lib.mpe_shard_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mpe_shard_bounds.restype = None
     lib.mpe_estimate_batch_multi.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
@@ -204,11 +206,13 @@ def load_library():
     return lib
 
 
-def tracker_estimate_batch(trackers, imgs, times):
+def tracker_estimate_batch(trackers, imgs, times, mixed=False):
     """mpe_tracker_estimate_batch: frame k of N trackers (same handle / camera / markers / parameters) in lock step,
     one device submission per step in steady state.  imgs: list of (rows, cols) uint8 arrays; times: N floats.
+    mixed: mpe_tracker_estimate_batch_mixed (the trackers may differ in camera, markers and parameters).
     -> (records [RESULT_DTYPE] (N), info (N,8) int32, updated (N) bool)."""
     lib = load_library()
+    name = "mpe_tracker_estimate_batch_mixed" if mixed else "mpe_tracker_estimate_batch"
     n = len(trackers)
     imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
     rows, cols = imgs[0].shape
@@ -220,19 +224,26 @@ def tracker_estimate_batch(trackers, imgs, times):
     rec = np.zeros(n, RESULT_DTYPE)
     info = np.zeros((n, 8), np.int32)
     upd = np.zeros(n, np.int32)
-    rc = lib.mpe_tracker_estimate_batch(ts, n, ptrs, rows, cols, stride, _dp(times), rec.ctypes.data, info.ctypes.data,
-                                        upd.ctypes.data)
+    rc = getattr(lib, name)(ts, n, ptrs, rows, cols, stride, _dp(times), rec.ctypes.data, info.ctypes.data,
+                            upd.ctypes.data)
     if rc < 0:
-        raise MpeError("mpe_tracker_estimate_batch failed (%d): %s"
-                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
+        raise MpeError("%s failed (%d): %s" % (name, rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
     return rec, info, upd.astype(bool)
 
 
-def tracker_run_sequences_batch(trackers, frames, times, threads=1):
+def tracker_estimate_batch_mixed(trackers, imgs, times):
+    """mpe_tracker_estimate_batch_mixed: as tracker_estimate_batch for distinct trackers on ONE handle that may differ
+    in camera (K, D), marker set and parameters — e.g. the cameras of a multi-camera rig."""
+    return tracker_estimate_batch(trackers, imgs, times, mixed=True)
+
+
+def tracker_run_sequences_batch(trackers, frames, times, threads=1, mixed=False):
     """mpe_tracker_run_sequences_batch[_threads]: the lock-step loop in C.  frames: list of (n,rows,cols) uint8 arrays
     (one sequence per tracker), times: n floats; threads > 1: the handle groups on that many host threads.
+    mixed: mpe_tracker_run_sequences_batch_mixed_threads (groups by handle alone, each may mix set-ups).
     -> (records (N,n), info (N,n,8))."""
     lib = load_library()
+    name = "mpe_tracker_run_sequences_batch_mixed_threads" if mixed else "mpe_tracker_run_sequences_batch_threads"
     N = len(trackers)
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     n, rows, cols = frames[0].shape
@@ -242,13 +253,17 @@ def tracker_run_sequences_batch(trackers, frames, times, threads=1):
     times = _f64(times).reshape(-1)
     rec = np.zeros((N, n), RESULT_DTYPE)
     info = np.zeros((N, n, 8), np.int32)
-    rc = lib.mpe_tracker_run_sequences_batch_threads(ts, N, ptrs, n, rows, cols, frames[0].strides[1],
-                                                     frames[0].strides[0], _dp(times), rec.ctypes.data,
-                                                     info.ctypes.data, int(threads))
+    rc = getattr(lib, name)(ts, N, ptrs, n, rows, cols, frames[0].strides[1], frames[0].strides[0], _dp(times),
+                            rec.ctypes.data, info.ctypes.data, int(threads))
     if rc < 0:
-        raise MpeError("mpe_tracker_run_sequences_batch failed (%d): %s"
-                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
+        raise MpeError("%s failed (%d): %s" % (name, rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
     return rec, info
+
+
+def tracker_run_sequences_batch_mixed(trackers, frames, times, threads=1):
+    """mpe_tracker_run_sequences_batch_mixed_threads: as tracker_run_sequences_batch, each handle's trackers one
+    lock-step group that may mix cameras, marker sets and parameters."""
+    return tracker_run_sequences_batch(trackers, frames, times, threads, mixed=True)
 
 
 class PinnedFrames:

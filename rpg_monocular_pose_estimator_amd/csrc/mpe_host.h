@@ -94,7 +94,23 @@ struct mpe_handle {
     const uint8_t* d_pix = nullptr;
     const void* d_wins = nullptr;
     const double* d_pred = nullptr;
+    // a submission of mpe_track_step_batch_setups_submit (streams of different set-ups): the slots are grouped by set-up,
+    // range r = slots [begin, begin + count) with its own parameters; slot k holds the caller's item perm[k]
+    struct Range {
+      int begin = 0, count = 0;
+      bool optimistic = false, fused = false;
+      DetectParams dp;
+      SolveParams sp;
+      double nn_tol = 0;
+    };
+    bool setups = false;
+    std::vector<Range> ranges;
+    std::vector<int> perm;
   } pending_track;
+  // counters of the lock-step batch entries (get "track_batch_submits" / "_chains" / "_reruns"): device submissions;
+  // set-ups of a submission that ran through the chain of kernels instead of the one launch (k_track_frame); set-ups
+  // of a submission repeated through that chain in _collect (a slot overflowed the small blob tier)
+  long long track_batch_submits = 0, track_batch_chains = 0, track_batch_reruns = 0;
   int pending_track_n = 0;            // mpe_track_step_batch_submit without its _collect yet: streams in flight
   const uint8_t* pending_track_rec = nullptr;
   // How many detections the frames of a pipelined call are expected to carry: picks the voting-kernel variant (from 9

@@ -157,6 +157,17 @@ struct TrackFramesArgs {
 size_t track_flag_words(const FrameGeom& g);
 hipError_t launch_track_frames(const TrackFramesArgs& t, int n_frames, const FrameGeom& g, const DetectParams& dp,
                                const SolveParams& sp, double nn_tol, hipStream_t s);
+// The same launch for a submission whose streams differ in camera, marker set and parameters: one TrackSetup per set-up
+// (built by make_detect_params / make_solve_params, as the uniform launch's arguments are), slot b runs with
+// setups[slot_setup[b]]; both arrays in device memory.  Optimistic set-ups only (1 .. 8 markers); max_markers sizes the
+// dynamic LDS for the largest of them.
+struct TrackSetup {
+  DetectParams dp;
+  SolveParams sp;
+  double nn_tol;  // nearest_neighbour_pixel_tolerance
+};
+hipError_t launch_track_frames_setups(const TrackFramesArgs& t, int n_frames, const FrameGeom& g, const TrackSetup* setups,
+                                      const int* slot_setup, int max_markers, hipStream_t s);
 hipError_t launch_repack(const uint8_t* src, size_t src_stride, size_t src_frame_stride, int n_frames, int roi_x,
                          int roi_y, int roi_w, int roi_h, uint8_t* dst, int dst_pitch, hipStream_t s);
 

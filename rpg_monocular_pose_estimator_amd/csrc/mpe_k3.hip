@@ -1003,9 +1003,44 @@ __device__ __forceinline__ void track_copy_words(void* dst, const void* src, uns
 }
 // CLOCKS (option "track_phase_clocks"): the shader clock at the five phase boundaries -> clk[0 .. 4] (s_memtime)
 #define K_TRACK_THREADS 256  // wave 0 runs the frame; waves 1 .. 3 take their share of the blur's items (k1b_wave<C, true>)
-template <bool CLOCKS>
-__global__ __launch_bounds__(K_TRACK_THREADS) void k_track_frame(TrackFrames a, FrameGeom g, DetectParams dp, SolveParams sp,
-                                                                 ThrTest thr, double nn_tol, int row_cap) {
+// The set-up of block b — dp, sp, thr, nn_tol, row_cap — is the launch's kernel arguments (the uniform launch,
+// k_track_frame<CLOCKS>), or, in k_track_frame<CLOCKS, const TrackSetup*, const int*> (mpe_track_step_batch_setups: the
+// streams of one time step differ in camera, marker set and parameters), entry slot_setup[b] of a set-up table that came
+// in the submission's input copy, built on the host by make_detect_params / make_solve_params exactly as the uniform
+// launch's arguments are: every block computes what k_track_frame computes for a launch of its set-up alone.  The
+// table's addresses are block-uniform and it is read-only for the launch: every wave (the helper waves too: the blur
+// reads dp) loads what it uses with scalar loads, as it loads kernel arguments.  Same barriers in both.
+struct TrackArgSetup {  // (the uniform launch: references to its kernel arguments)
+  const DetectParams& dp;
+  const SolveParams& sp;
+  ThrTest thr;
+  double nn_tol;
+  int row_cap;
+};
+__device__ __forceinline__ TrackArgSetup track_setup(const DetectParams& dp, const SolveParams& sp, ThrTest thr, double nn_tol,
+                                                     int row_cap) {
+  return TrackArgSetup{dp, sp, thr, nn_tol, row_cap};
+}
+__device__ __forceinline__ TrackArgSetup track_setup(const DetectParams&, const SolveParams&, ThrTest, double, int,
+                                                     const TrackSetup* setups, const int* slot_setup) {
+  // (through the constant address space: the compiler cannot prove on its own that the kernel's stores leave the table
+  //  alone, and would load every field with vector loads)
+  typedef __attribute__((address_space(4))) const TrackSetup* ConstSetups;
+  typedef __attribute__((address_space(4))) const int* ConstInts;
+  const int k = ((ConstInts)slot_setup)[blockIdx.x];
+  const TrackSetup& su = *(const TrackSetup*)((ConstSetups)setups + k);
+  return TrackArgSetup{su.dp, su.sp, make_thr_test(su.dp.thr), su.nn_tol, su.sp.n_markers > 3 ? su.sp.n_markers : 4};
+}
+template <bool CLOCKS, typename... Table>
+__global__ __launch_bounds__(K_TRACK_THREADS) void k_track_frame(TrackFrames a, FrameGeom g, DetectParams dp_arg,
+                                                                 SolveParams sp_arg, ThrTest thr_arg, double nn_tol_arg,
+                                                                 int row_cap_arg, Table... table) {
+  const TrackArgSetup su = track_setup(dp_arg, sp_arg, thr_arg, nn_tol_arg, row_cap_arg, table...);
+  const DetectParams& dp = su.dp;
+  const SolveParams& sp = su.sp;
+  const ThrTest thr = su.thr;
+  const double nn_tol = su.nn_tol;
+  const int row_cap = su.row_cap;
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
   mpe_detections* det = a.dets + b;
@@ -1076,11 +1111,7 @@ __global__ __launch_bounds__(K_TRACK_THREADS) void k_track_frame(TrackFrames a, 
   deliver();
 }
 size_t track_flag_words(const FrameGeom& g) { return ((size_t)g.rows * g.pitch / 16 + 63) / 64 + 2; }
-hipError_t launch_track_frames(const TrackFramesArgs& t, int n_frames, const FrameGeom& g, const DetectParams& dp,
-                               const SolveParams& sp, double nn_tol, hipStream_t s) {
-  if (n_frames <= 0) return hipSuccess;
-  const int rows = sp.n_markers > 3 ? sp.n_markers : 4;
-  const size_t lds_a = ((size_t)K3_FRAMES_PER_BLOCK * K3_GROUP * 3 * sp.n_markers + (size_t)2 * (rows - 3) * 64) * sizeof(double);
+static TrackFrames track_frames_args(const TrackFramesArgs& t, const FrameGeom& g) {
   TrackFrames a;
   a.pix = t.pix;
   a.slot_bytes = t.slot_bytes;
@@ -1097,12 +1128,41 @@ hipError_t launch_track_frames(const TrackFramesArgs& t, int n_frames, const Fra
   a.h_corr = t.h_corr;
   a.h_res = t.h_res;
   a.clk = t.phase_clocks;
+  return a;
+}
+// dynamic LDS of the validation body for a set-up of n_markers (k3a_body: per-lane contributions + back-projections)
+static size_t track_lds_bytes(int n_markers) {
+  const int rows = n_markers > 3 ? n_markers : 4;
+  return ((size_t)K3_FRAMES_PER_BLOCK * K3_GROUP * 3 * n_markers + (size_t)2 * (rows - 3) * 64) * sizeof(double);
+}
+hipError_t launch_track_frames(const TrackFramesArgs& t, int n_frames, const FrameGeom& g, const DetectParams& dp,
+                               const SolveParams& sp, double nn_tol, hipStream_t s) {
+  if (n_frames <= 0) return hipSuccess;
+  const int rows = sp.n_markers > 3 ? sp.n_markers : 4;
+  const size_t lds_a = track_lds_bytes(sp.n_markers);
+  const TrackFrames a = track_frames_args(t, g);
   if (t.phase_clocks)
     hipLaunchKernelGGL(k_track_frame<true>, dim3((unsigned)n_frames), dim3(K_TRACK_THREADS), lds_a, s, a, g, dp, sp, make_thr_test(dp.thr),
                        nn_tol, rows);
   else
     hipLaunchKernelGGL(k_track_frame<false>, dim3((unsigned)n_frames), dim3(K_TRACK_THREADS), lds_a, s, a, g, dp, sp, make_thr_test(dp.thr),
                        nn_tol, rows);
+  return hipGetLastError();
+}
+hipError_t launch_track_frames_setups(const TrackFramesArgs& t, int n_frames, const FrameGeom& g, const TrackSetup* setups,
+                                      const int* slot_setup, int max_markers, hipStream_t s) {
+  if (n_frames <= 0) return hipSuccess;
+  const size_t lds_a = track_lds_bytes(max_markers);  // (every block lays its set-up's buffers out from the start)
+  const TrackFrames a = track_frames_args(t, g);
+  const DetectParams dp0 = {};  // (the set-up of a block comes from the table: these arguments are not read)
+  const SolveParams sp0 = {};
+  const ThrTest thr0 = {0u, 0u};
+  if (t.phase_clocks)
+    hipLaunchKernelGGL((k_track_frame<true, const TrackSetup*, const int*>), dim3((unsigned)n_frames), dim3(K_TRACK_THREADS),
+                       lds_a, s, a, g, dp0, sp0, thr0, 0.0, 4, setups, slot_setup);
+  else
+    hipLaunchKernelGGL((k_track_frame<false, const TrackSetup*, const int*>), dim3((unsigned)n_frames), dim3(K_TRACK_THREADS),
+                       lds_a, s, a, g, dp0, sp0, thr0, 0.0, 4, setups, slot_setup);
   return hipGetLastError();
 }
 

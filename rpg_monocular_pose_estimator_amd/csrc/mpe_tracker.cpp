@@ -613,10 +613,11 @@ struct BatchLane {
   int error = 0;          // per-stream capacity status (< 0) that ended this stream's frame
 };
 
-bool same_setup(const mpe_tracker* a, const mpe_tracker* b) {
-  return a->h == b->h && a->markers == b->markers && a->D == b->D && !std::memcmp(a->K, b->K, sizeof(a->K)) &&
+bool same_camera_markers_params(const mpe_tracker* a, const mpe_tracker* b) {
+  return a->markers == b->markers && a->D == b->D && !std::memcmp(a->K, b->K, sizeof(a->K)) &&
          !std::memcmp(&a->p, &b->p, sizeof(mpe_params));
 }
+bool same_setup(const mpe_tracker* a, const mpe_tracker* b) { return a->h == b->h && same_camera_markers_params(a, b); }
 
 struct BatchCtx {
   mpe_tracker* const* ts = nullptr;
@@ -633,15 +634,38 @@ struct BatchCtx {
   std::vector<mpe_detections> dets;
   std::vector<uint32_t> corr;
   std::vector<mpe_result> res;
+  // mixed groups (the *_mixed entries): the lanes' set-ups — camera, markers, parameters — as mpe_track_setup entries
+  // pointing into the first tracker of each set-up, and the set-up of every lane
+  bool mixed = false;
+  std::vector<mpe_track_setup> setups;
+  std::vector<int> lane_setup, item_setup;
 
-  int validate(mpe_tracker* const* ts_, int n_) {
+  int validate(mpe_tracker* const* ts_, int n_, bool mixed_ = false) {
     ts = ts_;
     n = n_;
+    mixed = mixed_;
     for (int i = 0; i < n; ++i) {
       if (!ts[i]) return MPE_ERR_ARG;
-      if (!same_setup(ts[0], ts[i])) return MPE_ERR_ARG;  // one handle, camera model, marker set, parameter set
+      if (mixed ? ts[i]->h != ts[0]->h : !same_setup(ts[0], ts[i]))
+        return MPE_ERR_ARG;  // one handle (and, uniform, one camera model, marker set, parameter set)
       for (int j = 0; j < i; ++j)
         if (ts[j] == ts[i]) return MPE_ERR_ARG;
+    }
+    setups.clear();
+    lane_setup.assign((size_t)n, 0);
+    if (mixed) {
+      std::vector<int> first;  // first lane of every set-up
+      for (int i = 0; i < n; ++i) {
+        size_t s = 0;
+        while (s < first.size() && !same_camera_markers_params(ts[first[s]], ts[i])) ++s;
+        if (s == first.size()) {
+          const mpe_tracker* t = ts[i];
+          first.push_back(i);
+          setups.push_back(mpe_track_setup{&t->p, t->K, t->D.empty() ? nullptr : t->D.data(), (int)t->D.size(),
+                                           t->markers.data(), n_markers(t)});
+        }
+        lane_setup[(size_t)i] = (int)s;
+      }
     }
     h = ts[0]->h;
     nm = n_markers(ts[0]);
@@ -673,7 +697,7 @@ struct BatchCtx {
       } else {
         if (t->it_since_initialized >= 2)
           t->predicted = predict_pose(t->current, t->previous, t->t_current, t->t_previous, t->t_predicted);
-        for (int k = 0; k < nm; ++k)
+        for (int k = 0; k < n_markers(t); ++k)
           project(t, t->predicted, &t->markers[3 * k], t->predicted_px[2 * k], t->predicted_px[2 * k + 1]);
         determine_roi(t, rows, cols);
         L[(size_t)i].tracking = true;
@@ -688,6 +712,7 @@ struct BatchCtx {
   // ROI slot of the batch); returns the number of lanes submitted or < 0
   int submit_detect(int big) {
     items.clear();
+    item_setup.clear();
     pend.clear();
     for (int i = 0; i < n; ++i) {
       if (L[(size_t)i].op != OP_DETECT || (int)is_big(i) != big) continue;
@@ -700,11 +725,14 @@ struct BatchCtx {
       it.roi_h = t->roi[3];
       it.predicted_px = L[(size_t)i].tracking ? t->predicted_px.data() : nullptr;
       items.push_back(it);
+      item_setup.push_back(lane_setup[(size_t)i]);
       pend.push_back(i);
     }
     if (items.empty()) return 0;
-    const int rc = mpe_track_step_batch_submit(h, items.data(), (int)items.size(), rows, cols, stride, &ts[0]->p, ts[0]->K,
-                                               Dp, nD, ts[0]->markers.data(), nm);
+    const int rc = mixed ? mpe_track_step_batch_setups_submit(h, items.data(), item_setup.data(), (int)items.size(), rows,
+                                                              cols, stride, setups.data(), (int)setups.size())
+                         : mpe_track_step_batch_submit(h, items.data(), (int)items.size(), rows, cols, stride, &ts[0]->p,
+                                                       ts[0]->K, Dp, nD, ts[0]->markers.data(), nm);
     if (rc != MPE_OK) {
       pend.clear();
       return rc;
@@ -769,12 +797,21 @@ struct BatchCtx {
     return MPE_OK;
   }
 
-  // brute-force (re-)initialisations requested so far, one submission
+  // brute-force (re-)initialisations requested so far: one submission, or one per set-up that has any (mixed group)
   int brute() {
+    if (!mixed) return brute_setup(-1);
+    for (size_t s = 0; s < setups.size(); ++s) {
+      const int rc = brute_setup((int)s);
+      if (rc != MPE_OK) return rc;
+    }
+    return MPE_OK;
+  }
+  int brute_setup(int setup) {  // (-1: every lane, uniform group)
     std::vector<int> idx;
     for (int i = 0; i < n; ++i)
-      if (L[(size_t)i].op == OP_BRUTE) idx.push_back(i);
+      if (L[(size_t)i].op == OP_BRUTE && (setup < 0 || lane_setup[(size_t)i] == setup)) idx.push_back(i);
     if (idx.empty()) return MPE_OK;
+    const mpe_tracker* t0 = ts[idx[0]];  // (the set-up of these lanes)
     const int m = (int)idx.size();
     std::vector<double> det_xy((size_t)m * 2 * MPE_MAX_DETECTIONS, 0.0);
     std::vector<int> nd((size_t)m);
@@ -785,8 +822,8 @@ struct BatchCtx {
     }
     res.resize((size_t)m);
     std::vector<uint32_t> hist((size_t)m * MPE_MAX_DETECTIONS * MPE_MAX_MARKERS), bc((size_t)m * 2 * MPE_MAX_MARKERS);
-    const int rc = mpe_solve_bruteforce_batch(h, det_xy.data(), nd.data(), m, ts[0]->markers.data(), nm, ts[0]->K, &ts[0]->p,
-                                              res.data(), hist.data(), bc.data());
+    const int rc = mpe_solve_bruteforce_batch(h, det_xy.data(), nd.data(), m, t0->markers.data(), n_markers(t0), t0->K,
+                                              &t0->p, res.data(), hist.data(), bc.data());
     if (rc != MPE_OK) return rc;
     for (int k = 0; k < m; ++k) {
       const int i = idx[(size_t)k];
@@ -887,14 +924,14 @@ struct BatchCtx {
 
 extern "C" {
 
-int mpe_tracker_estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
-                               size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated) {
+static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
+                          size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated, bool mixed) {
   if (!ts || n < 0 || !imgs || !times) return MPE_ERR_ARG;
   if (n == 0) return 0;
   for (int i = 0; i < n; ++i)
     if (!imgs[i]) return MPE_ERR_ARG;
   BatchCtx c;
-  int rc = c.validate(ts, n);
+  int rc = c.validate(ts, n, mixed);
   if (rc != MPE_OK) return rc;
   c.begin(imgs, rows, cols, stride_bytes, times);
   if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
@@ -904,13 +941,24 @@ int mpe_tracker_estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* con
   return c.outputs(out, 1, info, 8, updated);
 }
 
+int mpe_tracker_estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
+                               size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated) {
+  return estimate_batch(ts, n, imgs, rows, cols, stride_bytes, times, out, info, updated, false);
+}
+
+int mpe_tracker_estimate_batch_mixed(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
+                                     size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated) {
+  return estimate_batch(ts, n, imgs, rows, cols, stride_bytes, times, out, info, updated, true);
+}
+
 // The lock-step loops of N streams over recorded sequences.  Trackers that live on DIFFERENT handles form groups
 // (one group per handle, each with the same camera / marker / parameter set inside the group); the groups are
 // pipelined against each other: while the device works on step k of one group, the host collects, advances and
 // packs another — the host work of a time step (~3 us per stream) hides behind the device latency (~0.2 ms).
-int mpe_tracker_run_sequences_batch_threads(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames,
-                                            int rows, int cols, size_t stride_bytes, size_t frame_stride_bytes,
-                                            const double* times, mpe_result* out, int* info, int n_threads) {
+// (mixed: each group may mix cameras, marker sets and parameters — mpe_tracker_run_sequences_batch_mixed_threads)
+static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows, int cols,
+                               size_t stride_bytes, size_t frame_stride_bytes, const double* times, mpe_result* out,
+                               int* info, int n_threads, bool mixed) {
   if (!ts || n < 0 || !frames || !times || n_frames < 0 || n_threads < 1) return MPE_ERR_ARG;
   if (n == 0 || n_frames == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -936,7 +984,7 @@ int mpe_tracker_run_sequences_batch_threads(mpe_tracker* const* ts, int n, const
     for (int i : members[g]) gts[g].push_back(ts[i]);
     gimgs[g].resize(members[g].size());
     gtimes[g].resize(members[g].size());
-    const int rc = ctx[g].validate(gts[g].data(), (int)gts[g].size());
+    const int rc = ctx[g].validate(gts[g].data(), (int)gts[g].size(), mixed);
     if (rc != MPE_OK) return rc;
   }
   // The groups gs[0..) on the calling thread, pipelined against each other: while the device works on step k of one
@@ -1003,6 +1051,21 @@ int mpe_tracker_run_sequences_batch_threads(mpe_tracker* const* ts, int n, const
     updated += upd[t];
   }
   return (int)std::min<long long>(updated, 0x7fffffff);
+}
+
+int mpe_tracker_run_sequences_batch_threads(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames,
+                                            int rows, int cols, size_t stride_bytes, size_t frame_stride_bytes,
+                                            const double* times, mpe_result* out, int* info, int n_threads) {
+  return run_sequences_batch(ts, n, frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
+                             n_threads, false);
+}
+
+int mpe_tracker_run_sequences_batch_mixed_threads(mpe_tracker* const* ts, int n, const uint8_t* const* frames,
+                                                  int n_frames, int rows, int cols, size_t stride_bytes,
+                                                  size_t frame_stride_bytes, const double* times, mpe_result* out,
+                                                  int* info, int n_threads) {
+  return run_sequences_batch(ts, n, frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
+                             n_threads, true);
 }
 
 int mpe_tracker_run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows,

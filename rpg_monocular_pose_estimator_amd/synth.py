@@ -195,13 +195,17 @@ def make_frames(config, n, seed):
                 rows=cfg["rows"], cols=cfg["cols"])
 
 
-def make_sequence(config, n, seed, dt=0.02, lin_speed=0.15, ang_speed=0.6, dropout=(), salt=0.0):
+def make_sequence(config, n, seed, dt=0.02, lin_speed=0.15, ang_speed=0.6, dropout=(), salt=0.0, camera=None):
     """A smooth trajectory (constant body twist + small jitter) for the tracking path: frame k is at
     time k*dt.  Frames listed in `dropout` are rendered with only 2 LEDs (forces the retry /
     re-initialisation logic); `salt`: that fraction of every frame's pixels saturated (isolated bright pixels inside
-    and outside the ROI).  -> dict(frames, T_true, times, K, D, markers)"""
+    and outside the ROI); `camera`: (K, D) of another camera (5 plumb-bob coefficients) instead of the README camera —
+    the cameras of a multi-camera rig.  -> dict(frames, T_true, times, K, D, markers)"""
     cfg = CONFIGS[config] if isinstance(config, str) else config
-    K, D = camera_for(cfg["rows"], cfg["cols"])
+    if camera is None:
+        K, D = camera_for(cfg["rows"], cfg["cols"])
+    else:
+        K, D = np.array(camera[0], np.float64).reshape(3, 3), np.array(camera[1], np.float64).reshape(-1)
     rows, cols, M = cfg["rows"], cfg["cols"], np.asarray(cfg["markers"])
     rng = np.random.default_rng([seed, 7])
     while True:
