@@ -81,29 +81,22 @@ struct mpe_handle {
   // host-side time of the tracked frame (option "track_profile" = 1 starts / resets): sums in ns
   int track_profile = 0;
   long long track_ns[3] = {0, 0, 0}, track_steps = 0;  // pack, enqueue, wait
-  // what mpe_track_step_batch_collect needs to repeat a submission whose blobs overflowed the small tier
+  // the lock-step submission in flight (mpe_track_abi.cpp submit_slots, for both batch submit entries), as
+  // mpe_track_step_batch_collect needs it to repeat the set-ups whose slots overflowed the small blob tier and to hand
+  // out the records: the slots are grouped by set-up (a uniform batch is one set-up), range r = slots
+  // [begin, begin + count) with its set-up's parameters; slot k holds the caller's item perm[k]
   struct PendingTrack {
-    bool optimistic = false;
-    bool fused = false;        // the submission ran as k_track_frame: its flag words are per block, not the scan's bitstream
-    size_t slot_bytes = 0;
     FrameGeom g;
-    DetectParams dp;
-    SolveParams sp;
-    double nn_tol = 0;
-    size_t rec_bytes = 0;
+    size_t slot_bytes = 0, rec_bytes = 0;
     const uint8_t* d_pix = nullptr;
     const void* d_wins = nullptr;
     const double* d_pred = nullptr;
-    // a submission of mpe_track_step_batch_setups_submit (streams of different set-ups): the slots are grouped by set-up,
-    // range r = slots [begin, begin + count) with its own parameters; slot k holds the caller's item perm[k]
     struct Range {
       int begin = 0, count = 0;
-      bool optimistic = false, fused = false;
-      DetectParams dp;
-      SolveParams sp;
-      double nn_tol = 0;
+      bool optimistic = false;  // 1 .. 8 markers: the small blob tier alone, the whole chain again in _collect if need be
+      bool fused = false;       // in the one launch (k_track_frame), not through the chain of kernels
+      TrackSetup su;
     };
-    bool setups = false;
     std::vector<Range> ranges;
     std::vector<int> perm;
   } pending_track;
@@ -111,8 +104,8 @@ struct mpe_handle {
   // set-ups of a submission that ran through the chain of kernels instead of the one launch (k_track_frame); set-ups
   // of a submission repeated through that chain in _collect (a slot overflowed the small blob tier)
   long long track_batch_submits = 0, track_batch_chains = 0, track_batch_reruns = 0;
-  int pending_track_n = 0;            // mpe_track_step_batch_submit without its _collect yet: streams in flight
-  const uint8_t* pending_track_rec = nullptr;
+  int pending_track_n = 0;            // a batch submission without its _collect yet: streams in flight
+  uint8_t* pending_track_rec = nullptr;
   // How many detections the frames of a pipelined call are expected to carry: picks the voting-kernel variant (from 9
   // on: the scan-carrying kernel with an occupancy grid of the detections, mpe_k2.hip K2_CGRID) and sizes the suspect
   // lists.  Never a matter of correctness.  Option "detections_hint" (0 = automatic: the number of markers, or what the

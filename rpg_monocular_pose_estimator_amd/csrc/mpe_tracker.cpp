@@ -626,16 +626,15 @@ struct BatchCtx {
   int rows = 0, cols = 0;
   size_t stride = 0;
   mpe_handle* h = nullptr;
-  int nm = 0, nD = 0;
-  const double* Dp = nullptr;
   std::vector<BatchLane> L;
   std::vector<int> pend;  // lanes of the submitted, not yet collected DETECT batch
   std::vector<mpe_track_item> items;
   std::vector<mpe_detections> dets;
   std::vector<uint32_t> corr;
   std::vector<mpe_result> res;
-  // mixed groups (the *_mixed entries): the lanes' set-ups — camera, markers, parameters — as mpe_track_setup entries
-  // pointing into the first tracker of each set-up, and the set-up of every lane
+  // the lanes' set-ups — camera, markers, parameters — as mpe_track_setup entries pointing into the first tracker of
+  // each set-up (a uniform group has one), and the set-up of every lane.  mixed (the *_mixed entries) admits lanes of
+  // different set-ups on one handle; otherwise every lane must have the first one's.
   bool mixed = false;
   std::vector<mpe_track_setup> setups;
   std::vector<int> lane_setup, item_setup;
@@ -653,24 +652,19 @@ struct BatchCtx {
     }
     setups.clear();
     lane_setup.assign((size_t)n, 0);
-    if (mixed) {
-      std::vector<int> first;  // first lane of every set-up
-      for (int i = 0; i < n; ++i) {
-        size_t s = 0;
-        while (s < first.size() && !same_camera_markers_params(ts[first[s]], ts[i])) ++s;
-        if (s == first.size()) {
-          const mpe_tracker* t = ts[i];
-          first.push_back(i);
-          setups.push_back(mpe_track_setup{&t->p, t->K, t->D.empty() ? nullptr : t->D.data(), (int)t->D.size(),
-                                           t->markers.data(), n_markers(t)});
-        }
-        lane_setup[(size_t)i] = (int)s;
+    std::vector<int> first;  // first lane of every set-up
+    for (int i = 0; i < n; ++i) {
+      size_t s = 0;
+      while (s < first.size() && !same_camera_markers_params(ts[first[s]], ts[i])) ++s;
+      if (s == first.size()) {
+        const mpe_tracker* t = ts[i];
+        first.push_back(i);
+        setups.push_back(mpe_track_setup{&t->p, t->K, t->D.empty() ? nullptr : t->D.data(), (int)t->D.size(),
+                                         t->markers.data(), n_markers(t)});
       }
+      lane_setup[(size_t)i] = (int)s;
     }
     h = ts[0]->h;
-    nm = n_markers(ts[0]);
-    Dp = ts[0]->D.empty() ? nullptr : ts[0]->D.data();
-    nD = (int)ts[0]->D.size();
     L.assign((size_t)n, BatchLane());
     return MPE_OK;
   }
@@ -729,10 +723,8 @@ struct BatchCtx {
       pend.push_back(i);
     }
     if (items.empty()) return 0;
-    const int rc = mixed ? mpe_track_step_batch_setups_submit(h, items.data(), item_setup.data(), (int)items.size(), rows,
-                                                              cols, stride, setups.data(), (int)setups.size())
-                         : mpe_track_step_batch_submit(h, items.data(), (int)items.size(), rows, cols, stride, &ts[0]->p,
-                                                       ts[0]->K, Dp, nD, ts[0]->markers.data(), nm);
+    const int rc = mpe_track_step_batch_setups_submit(h, items.data(), item_setup.data(), (int)items.size(), rows, cols,
+                                                      stride, setups.data(), (int)setups.size());
     if (rc != MPE_OK) {
       pend.clear();
       return rc;
@@ -797,19 +789,18 @@ struct BatchCtx {
     return MPE_OK;
   }
 
-  // brute-force (re-)initialisations requested so far: one submission, or one per set-up that has any (mixed group)
+  // brute-force (re-)initialisations requested so far: one submission per set-up that has any
   int brute() {
-    if (!mixed) return brute_setup(-1);
     for (size_t s = 0; s < setups.size(); ++s) {
       const int rc = brute_setup((int)s);
       if (rc != MPE_OK) return rc;
     }
     return MPE_OK;
   }
-  int brute_setup(int setup) {  // (-1: every lane, uniform group)
+  int brute_setup(int setup) {
     std::vector<int> idx;
     for (int i = 0; i < n; ++i)
-      if (L[(size_t)i].op == OP_BRUTE && (setup < 0 || lane_setup[(size_t)i] == setup)) idx.push_back(i);
+      if (L[(size_t)i].op == OP_BRUTE && lane_setup[(size_t)i] == setup) idx.push_back(i);
     if (idx.empty()) return MPE_OK;
     const mpe_tracker* t0 = ts[idx[0]];  // (the set-up of these lanes)
     const int m = (int)idx.size();

@@ -181,9 +181,13 @@ def test_mixed_group_equals_uniform_groups(mixed_run):
     hs = [mpe.Handle(0) for _ in S]
     ts = _trackers(hs, S, seqs)
     rec, info = mpe.tracker_run_sequences_batch(ts, [q["frames"] for q in seqs], seqs[0]["times"])
+    c = {k: sum(h.get_option(k) for h in hs) for k in ("track_batch_chains", "track_batch_reruns")}
     _close(ts, hs)
     assert rec.tobytes() == mixed_run["rec"].tobytes()
     assert np.array_equal(info, mixed_run["info"])
+    # the uniform groups take the same rare paths as the mixed one, and count them alike
+    assert c["track_batch_reruns"] >= 1, c                    # the salt stream overflowed the small tier
+    assert c["track_batch_chains"] >= N_FRAMES, c             # the 10-marker set-up: the chain of kernels every step
 
 
 @pytest.mark.gpu
@@ -266,14 +270,100 @@ def test_mixed_entry_with_one_setup_equals_uniform_entry():
     assert out[0][0].tobytes() == out[1][0].tobytes() and np.array_equal(out[0][1], out[1][1])
 
 
+class _TrackItem(ctypes.Structure):  # mpe_track_item
+    _fields_ = [("img", ctypes.c_void_p), ("roi_x", ctypes.c_int), ("roi_y", ctypes.c_int), ("roi_w", ctypes.c_int),
+                ("roi_h", ctypes.c_int), ("predicted_px", ctypes.c_void_p)]
+
+
+class _TrackSetup(ctypes.Structure):  # mpe_track_setup
+    _fields_ = [("p", ctypes.c_void_p), ("K", ctypes.c_void_p), ("D", ctypes.c_void_p), ("nD", ctypes.c_int),
+                ("markers_xyz", ctypes.c_void_p), ("n_markers", ctypes.c_int)]
+
+
 @pytest.mark.gpu
-def test_mixed_steady_state_step_is_one_submission():
+def test_submit_entries_refuse_bad_usage_and_stay_usable():
+    """Usage errors of both submit entries on a real handle: their codes and messages, no submission counted, and the
+    handle still takes a valid submit + collect afterwards, whose records are those of the first valid one."""
+    lib = mpe.load_library()
+    q = synth.make_sequence("C2", 1, seed=990)
+    rows, cols = int(q["rows"]), int(q["cols"])
+    img = np.ascontiguousarray(q["frames"][0])
+    K, D = np.ascontiguousarray(q["K"], np.float64), np.ascontiguousarray(q["D"], np.float64)
+    markers = np.ascontiguousarray(q["markers"], np.float64)
+    m17 = np.zeros((17, 3))
+    P, P_sigma0 = mpe.demo_params(), mpe.demo_params(gaussian_sigma=0.0)
+    pred = np.ascontiguousarray(synth.project(q["T_true"][0], q["markers"], q["K"]), np.float64)
+    px = synth.distort_px(pred, q["K"], q["D"])
+    x0, y0 = [max(0, int(v) - 40) for v in px.min(0)]
+    x1, y1 = min(cols, int(px[:, 0].max()) + 40), min(rows, int(px[:, 1].max()) + 40)
+    h = mpe.Handle(0)
+    hp = h._h
+
+    def items(roi_x=0):
+        it = (_TrackItem * 2)()
+        it[0] = _TrackItem(img.ctypes.data, roi_x, 0, cols, rows, None)                     # whole image, detection only
+        it[1] = _TrackItem(img.ctypes.data, x0, y0, x1 - x0, y1 - y0, pred.ctypes.data)      # tracked around the LEDs
+        return it
+
+    def ptr(a):
+        return ctypes.c_void_p(a.ctypes.data)
+
+    def submit(it, p=P, mk=markers, n_markers=len(markers)):
+        return lib.mpe_track_step_batch_submit(hp, it, 2, rows, cols, ctypes.c_size_t(img.strides[0]), ctypes.byref(p),
+                                               ptr(K), ptr(D), len(D), ptr(mk), n_markers)
+
+    def submit_setups(it, idx=(0, 0), mk=markers, n_markers=len(markers)):
+        su = (_TrackSetup * 1)(_TrackSetup(ctypes.addressof(P), K.ctypes.data, D.ctypes.data, len(D), mk.ctypes.data,
+                                           n_markers))
+        return lib.mpe_track_step_batch_setups_submit(hp, it, (ctypes.c_int * 2)(*idx), 2, rows, cols,
+                                                      ctypes.c_size_t(img.strides[0]), su, 1)
+
+    def collect():
+        dets, corr, res = np.zeros(2, mpe.DETECTIONS_DTYPE), np.zeros(2 * 32, np.uint32), np.zeros(2, mpe.RESULT_DTYPE)
+        assert lib.mpe_track_step_batch_collect(hp, ptr(dets), ptr(corr), ptr(res)) == 0
+        return dets.tobytes() + corr.tobytes() + res.tobytes()
+
+    def refused(rc, code, text):
+        assert rc == code, (rc, code, text)
+        assert text in lib.mpe_last_error(hp).decode(), lib.mpe_last_error(hp).decode()
+
+    try:
+        assert submit(items()) == 0
+        ref = collect()
+        n0 = h.get_option("track_batch_submits")
+        cases = [(submit, dict(it=items(roi_x=1)), -1, "ROI outside the image"),
+                 (submit, dict(it=items(), mk=m17, n_markers=17), -3, "n_markers > MPE_MAX_MARKERS"),
+                 (submit, dict(it=items(), p=P_sigma0), -1, "gaussian_sigma must be in (0, 6]"),
+                 (submit_setups, dict(it=items(), idx=(0, 1)), -1, "set-up index out of range"),
+                 (submit_setups, dict(it=items(), idx=(-1, 0)), -1, "set-up index out of range"),
+                 (submit_setups, dict(it=items(), mk=m17, n_markers=17), -1, "set-up with n_markers > MPE_MAX_MARKERS")]
+        for entry, kw, code, text in cases:
+            refused(entry(**kw), code, text)
+            assert h.get_option("track_batch_submits") == n0, text
+            assert entry(items()) == 0, text
+            assert collect() == ref, text
+            n0 += 1
+        for entry in (submit, submit_setups):   # a second submit while one is pending
+            assert entry(items()) == 0
+            refused(submit(items()), -1, "a submitted batch has not been collected yet")
+            refused(submit_setups(items()), -1, "a submitted batch has not been collected yet")
+            assert collect() == ref
+            assert entry(items()) == 0 and collect() == ref
+        assert h.get_option("track_batch_submits") == n0 + 4
+    finally:
+        lib.mpe_track_step_batch_cancel(hp)
+        h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mixed", [True, False], ids=["mixed", "uniform"])
+def test_mixed_steady_state_step_is_one_submission(mixed):
     """A time step on which every stream is tracking and none retries, re-initialises or needs the large size class
     costs the whole mixed group (three set-ups: two cameras, two parameter sets) exactly one device submission — one
-    launch of k_track_frame — and no chain of kernels."""
-    S = [_setups()[i] for i in (0, 1, 4)]
+    launch of k_track_frame — and no chain of kernels.  So does a uniform group of as many streams (one set-up)."""
+    S = [_setups()[i] for i in ((0, 1, 4) if mixed else (0,))]
     seqs = []
-    for j in range(3 * len(S)):
+    for j in range(9):
         name, cfg, cam, kw = S[j % len(S)]
         seqs.append(synth.make_sequence(cfg, 16, seed=970 + j, camera=cam))
     h = mpe.Handle(0)
@@ -285,7 +375,8 @@ def test_mixed_steady_state_step_is_one_submission():
     seen = []
     for k in range(16):
         c0 = [h.get_option(x) for x in names]
-        r, info, upd = mpe.tracker_estimate_batch_mixed(ts, [q["frames"][k] for q in seqs], [seqs[0]["times"][k]] * len(seqs))
+        r, info, upd = mpe.tracker_estimate_batch(ts, [q["frames"][k] for q in seqs], [seqs[0]["times"][k]] * len(seqs),
+                                                  mixed=mixed)
         d = [h.get_option(x) - c for x, c in zip(names, c0)]
         small = (info[:, 2].astype(np.int64) * info[:, 3] * 4 <= rows * cols).all()
         seen.append((k, d, prev_it.tolist(), bool(small), int(info[:, 7].sum())))
