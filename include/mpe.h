@@ -302,7 +302,9 @@ int mpe_distort_points(const float* src_xy, float* dst_xy, int n, const double K
  * dets_out: what findLeds found (always written); corr_out: 2*MPE_MAX_MARKERS uint32, rows
  * (marker, detection) 1-based, out->n_corr rows valid; out->status 0 = pose refined, 1 = fewer than
  * 4 LEDs or correspondences rejected (the caller then retries / re-initialises as the reference does),
- * <0 = a device capacity was exceeded.  mpe_tracker_estimate uses this for every tracked frame. */
+ * <0 = a device capacity was exceeded.  The submission is that of mpe_track_step_batch with one item (refused, like
+ * _submit, while a lock-step submission of the handle is pending); mpe_tracker_estimate makes the same submissions
+ * through mpe_track_step_batch_setups_submit / _collect. */
 int mpe_track_step(mpe_handle* h, const uint8_t* img, int rows, int cols, size_t stride_bytes, int roi_x,
                    int roi_y, int roi_w, int roi_h, const mpe_params* p, const double K[9], const double* D,
                    int nD, const double* markers_xyz, int n_markers, const double* predicted_px,
@@ -543,10 +545,13 @@ int mpe_set_option(mpe_handle* h, const char* name, int value);
  * set "vote_events" = N > 0: a pair of timing events is recorded around every voting launch that carries a scan, for
  *   the launches of the last N pipelined calls — nothing else, so a timed region stays what it is; get
  *   "vote_launch_ns_mean" / "vote_launches" (synchronises the handle's stream); set 0 to release the events.
- * set "track_profile" = 1 starts / resets host-side timers inside mpe_track_step; get "track_ns_pack",
- *   "track_ns_enqueue", "track_ns_wait" (mean ns per step), "track_steps".
- * get "track_batch_submits", "track_batch_chains", "track_batch_reruns": device submissions of the lock-step batch
- *   entries (mpe_track_step_batch[_setups][_submit], and the tracker entries on top of them), set-ups of a submission
+ * set "track_profile" = 1 starts / resets host-side timers of every tracked submission (mpe_track_step, the lock-step
+ *   batch entries and the tracker entries on top of them); get "track_ns_pack" (to the input copy issued),
+ *   "track_ns_enqueue" (to the last command queued), "track_ns_wait" (to the records in hand in _collect; mean ns per
+ *   step), "track_steps" (submissions collected).
+ * get "track_batch_submits", "track_batch_chains", "track_batch_reruns": device submissions of the tracked entries
+ *   (mpe_track_step, mpe_track_step_batch[_setups][_submit], and every tracker entry on top of them, a lone tracker's
+ *   mpe_tracker_estimate / mpe_tracker_run_sequence included), set-ups of a submission
  *   that ran through the chain of kernels instead of the one fused launch (track_fused 0, more than 8 markers), and
  *   set-ups repeated through that chain by _collect because a slot overflowed the small blob tier; since the handle was
  *   made.

@@ -168,42 +168,66 @@ int vote_batch_impl(mpe_handle* h, const double* det_xy, const int* n_det, int n
 }  // namespace
 
 namespace {
-int solve_bruteforce_impl(mpe_handle* h, const double* det_xy, int n_det, const double* markers_xyz, int n_markers,
-                          const double K[9], const mpe_params* p, mpe_result* out, uint32_t* hist, uint32_t* corr,
-                          int tail_mode) {
-  if (!h || (!det_xy && n_det > 0) || !markers_xyz || !K || !p || !out || n_det < 0)
-    return fail(h, MPE_ERR_ARG, "bad argument");
-  if (n_det > MPE_MAX_DETECTIONS) return fail(h, MPE_ERR_UNSUPPORTED, "n_det > MPE_MAX_DETECTIONS");
+// setImagePoints + initialise + optimiseAndUpdatePose for n detection sets in one submission: det_xy n x
+// MPE_MAX_DETECTIONS x 2, n_det[f] valid rows each; hist (optional) n x MPE_HIST_WORDS, corr (optional) n x
+// 2*MPE_MAX_MARKERS.  tail_mode 1 = validation only (mpe_initialise).  The caller has checked its pointers.
+int solve_bruteforce_impl(mpe_handle* h, const double* det_xy, const int* n_det, int n, const double* markers_xyz,
+                          int n_markers, const double K[9], const mpe_params* p, mpe_result* out, uint32_t* hist,
+                          uint32_t* corr, int tail_mode) {
   ENTER(h);
   SolveParams sp;
   if (make_solve_params(h, p, markers_xyz, n_markers, K, sp)) return fail(h, MPE_ERR_UNSUPPORTED, "n_markers > MPE_MAX_MARKERS");
-  mpe_detections hd;
-  std::memset(&hd, 0, sizeof(hd));
-  hd.n = n_det;
-  if (n_det) std::memcpy(hd.undist_xy, det_xy, sizeof(double) * 2 * n_det);
-  HIP_TRY(h, h->dets.reserve(sizeof(mpe_detections)));
-  HIP_TRY(h, h->hist.reserve(MPE_HIST_STRIDE * sizeof(uint32_t)));
-  HIP_TRY(h, h->results.reserve(sizeof(mpe_result)));
-  HIP_TRY(h, h->corr.reserve(2 * MPE_MAX_MARKERS * sizeof(uint32_t)));
-  HIP_TRY(h, h->mid.reserve(k3_mid_bytes(1)));
-  HIP_TRY(h, hipMemcpyAsync(h->dets.p, &hd, sizeof(hd), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemsetAsync(h->hist.p, 0, MPE_HIST_STRIDE * sizeof(uint32_t), h->stream));
+  std::vector<mpe_detections> hd((size_t)n);
+  int nd_max = 0;
+  for (int f = 0; f < n; ++f) {
+    std::memset(&hd[f], 0, sizeof(mpe_detections));
+    if (n_det[f] < 0 || n_det[f] > MPE_MAX_DETECTIONS) return fail(h, MPE_ERR_ARG, "n_det out of range");
+    hd[f].n = n_det[f];
+    nd_max = std::max(nd_max, n_det[f]);
+    std::memcpy(hd[f].undist_xy, det_xy + (size_t)f * 2 * MPE_MAX_DETECTIONS, sizeof(double) * 2 * n_det[f]);
+  }
+  const size_t hist_bytes = (size_t)n * MPE_HIST_STRIDE * sizeof(uint32_t);
+  const size_t corr_bytes = (size_t)n * 2 * MPE_MAX_MARKERS * sizeof(uint32_t);
+  HIP_TRY(h, h->dets.reserve((size_t)n * sizeof(mpe_detections)));
+  HIP_TRY(h, h->hist.reserve(hist_bytes));
+  HIP_TRY(h, h->results.reserve((size_t)n * sizeof(mpe_result)));
+  HIP_TRY(h, h->corr.reserve(corr_bytes));
+  HIP_TRY(h, h->mid.reserve(k3_mid_bytes(n)));
+  HIP_TRY(h, hipMemcpyAsync(h->dets.p, hd.data(), (size_t)n * sizeof(mpe_detections), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->hist.p, 0, hist_bytes, h->stream));
   { const int rc = prep_marker_table(h, sp); if (rc) return rc; }
   VoteFixup fx;
-  { const int rc = vote_fixup_for(h, 0, 1, 1, n_markers, n_det, h->stream, fx); if (rc) return rc; }
-  HIP_TRY(h, launch_k2_vote(static_cast<mpe_detections*>(h->dets.p), 1, sp, static_cast<const double*>(h->mtab.p),
-                            static_cast<uint32_t*>(h->hist.p), auto_splits(h, 1, n_markers), n_det, h->stream, nullptr,
+  { const int rc = vote_fixup_for(h, 0, 1, n, n_markers, nd_max, h->stream, fx); if (rc) return rc; }
+  HIP_TRY(h, launch_k2_vote(static_cast<mpe_detections*>(h->dets.p), n, sp, static_cast<const double*>(h->mtab.p),
+                            static_cast<uint32_t*>(h->hist.p), auto_splits(h, n, n_markers), nd_max, h->stream, nullptr,
                             0, nullptr, 0, nullptr, nullptr, &fx));
-  HIP_TRY(h, fixup_launch(h, 0, static_cast<mpe_detections*>(h->dets.p), 1, sp, static_cast<uint32_t*>(h->hist.p), fx,
+  HIP_TRY(h, fixup_launch(h, 0, static_cast<mpe_detections*>(h->dets.p), n, sp, static_cast<uint32_t*>(h->hist.p), fx,
                           h->stream));
-  HIP_TRY(h, launch_k3_tail(static_cast<mpe_detections*>(h->dets.p), static_cast<uint32_t*>(h->hist.p), 1, sp,
-                            static_cast<mpe_result*>(h->results.p), static_cast<uint32_t*>(h->corr.p), nullptr,
-                            nullptr, 0.0, h->mid.p, h->stream, tail_mode));
-  uint32_t hh[MPE_HIST_STRIDE], hc[2 * MPE_MAX_MARKERS];
-  HIP_TRY(h, hipMemcpyAsync(out, h->results.p, sizeof(mpe_result), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(hh, h->hist.p, sizeof(hh), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(hc, h->corr.p, sizeof(hc), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, launch_k3_tail(static_cast<mpe_detections*>(h->dets.p), static_cast<uint32_t*>(h->hist.p), n, sp,
+                            static_cast<mpe_result*>(h->results.p), static_cast<uint32_t*>(h->corr.p), nullptr, nullptr,
+                            0.0, h->mid.p, h->stream, tail_mode));
+  HIP_TRY(h, hipMemcpyAsync(out, h->results.p, (size_t)n * sizeof(mpe_result), hipMemcpyDeviceToHost, h->stream));
+  if (hist)  // (device rows are MPE_HIST_STRIDE words apart, the caller's MPE_HIST_WORDS)
+    HIP_TRY(h, hipMemcpy2DAsync(hist, MPE_HIST_WORDS * sizeof(uint32_t), h->hist.p, MPE_HIST_STRIDE * sizeof(uint32_t),
+                                MPE_HIST_WORDS * sizeof(uint32_t), (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  if (corr) HIP_TRY(h, hipMemcpyAsync(corr, h->corr.p, corr_bytes, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPE_OK;
+}
+
+// mpe_solve_bruteforce / mpe_initialise: one detection set of n_det rows; the compact n_det x n_markers histogram and
+// 2*n_markers correspondence words
+int solve_bruteforce_one(mpe_handle* h, const double* det_xy, int n_det, const double* markers_xyz, int n_markers,
+                         const double K[9], const mpe_params* p, mpe_result* out, uint32_t* hist, uint32_t* corr,
+                         int tail_mode) {
+  if (!h || (!det_xy && n_det > 0) || !markers_xyz || !K || !p || !out || n_det < 0)
+    return fail(h, MPE_ERR_ARG, "bad argument");
+  if (n_det > MPE_MAX_DETECTIONS) return fail(h, MPE_ERR_UNSUPPORTED, "n_det > MPE_MAX_DETECTIONS");
+  double xy[2 * MPE_MAX_DETECTIONS];
+  if (n_det) std::memcpy(xy, det_xy, sizeof(double) * 2 * n_det);
+  uint32_t hh[MPE_HIST_WORDS], hc[2 * MPE_MAX_MARKERS];
+  const int rc = solve_bruteforce_impl(h, xy, &n_det, 1, markers_xyz, n_markers, K, p, out, hh, hc, tail_mode);
+  if (rc != MPE_OK) return rc;
   if (hist)
     for (int r = 0; r < n_det; ++r)
       for (int c = 0; c < n_markers; ++c) hist[r * n_markers + c] = hh[r * MPE_MAX_MARKERS + c];
@@ -214,12 +238,12 @@ int solve_bruteforce_impl(mpe_handle* h, const double* det_xy, int n_det, const 
 
 int mpe_solve_bruteforce(mpe_handle* h, const double* det_xy, int n_det, const double* markers_xyz, int n_markers,
                          const double K[9], const mpe_params* p, mpe_result* out, uint32_t* hist, uint32_t* corr) {
-  return solve_bruteforce_impl(h, det_xy, n_det, markers_xyz, n_markers, K, p, out, hist, corr, 0);
+  return solve_bruteforce_one(h, det_xy, n_det, markers_xyz, n_markers, K, p, out, hist, corr, 0);
 }
 
 int mpe_initialise(mpe_handle* h, const double* det_xy, int n_det, const double* markers_xyz, int n_markers,
                    const double K[9], const mpe_params* p, mpe_result* out, uint32_t* hist, uint32_t* corr) {
-  return solve_bruteforce_impl(h, det_xy, n_det, markers_xyz, n_markers, K, p, out, hist, corr, 1);
+  return solve_bruteforce_one(h, det_xy, n_det, markers_xyz, n_markers, K, p, out, hist, corr, 1);
 }
 
 namespace {
@@ -552,45 +576,7 @@ int mpe_solve_bruteforce_batch(mpe_handle* h, const double* det_xy, const int* n
                                uint32_t* corr) {
   if (!h || !det_xy || !n_det || n < 0 || !markers_xyz || !K || !p || !out) return fail(h, MPE_ERR_ARG, "bad argument");
   if (n == 0) return MPE_OK;
-  ENTER(h);
-  SolveParams sp;
-  if (make_solve_params(h, p, markers_xyz, n_markers, K, sp)) return fail(h, MPE_ERR_UNSUPPORTED, "n_markers > MPE_MAX_MARKERS");
-  std::vector<mpe_detections> hd((size_t)n);
-  int nd_max = 0;
-  for (int f = 0; f < n; ++f) {
-    std::memset(&hd[f], 0, sizeof(mpe_detections));
-    if (n_det[f] < 0 || n_det[f] > MPE_MAX_DETECTIONS) return fail(h, MPE_ERR_ARG, "n_det out of range");
-    hd[f].n = n_det[f];
-    nd_max = std::max(nd_max, n_det[f]);
-    std::memcpy(hd[f].undist_xy, det_xy + (size_t)f * 2 * MPE_MAX_DETECTIONS, sizeof(double) * 2 * n_det[f]);
-  }
-  const size_t hist_bytes = (size_t)n * MPE_HIST_STRIDE * sizeof(uint32_t);
-  const size_t corr_bytes = (size_t)n * 2 * MPE_MAX_MARKERS * sizeof(uint32_t);
-  HIP_TRY(h, h->dets.reserve((size_t)n * sizeof(mpe_detections)));
-  HIP_TRY(h, h->hist.reserve(hist_bytes));
-  HIP_TRY(h, h->results.reserve((size_t)n * sizeof(mpe_result)));
-  HIP_TRY(h, h->corr.reserve(corr_bytes));
-  HIP_TRY(h, h->mid.reserve(k3_mid_bytes(n)));
-  HIP_TRY(h, hipMemcpyAsync(h->dets.p, hd.data(), (size_t)n * sizeof(mpe_detections), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemsetAsync(h->hist.p, 0, hist_bytes, h->stream));
-  { const int rc = prep_marker_table(h, sp); if (rc) return rc; }
-  VoteFixup fx;
-  { const int rc = vote_fixup_for(h, 0, 1, n, n_markers, nd_max, h->stream, fx); if (rc) return rc; }
-  HIP_TRY(h, launch_k2_vote(static_cast<mpe_detections*>(h->dets.p), n, sp, static_cast<const double*>(h->mtab.p),
-                            static_cast<uint32_t*>(h->hist.p), auto_splits(h, n, n_markers), nd_max, h->stream, nullptr,
-                            0, nullptr, 0, nullptr, nullptr, &fx));
-  HIP_TRY(h, fixup_launch(h, 0, static_cast<mpe_detections*>(h->dets.p), n, sp, static_cast<uint32_t*>(h->hist.p), fx,
-                          h->stream));
-  HIP_TRY(h, launch_k3_tail(static_cast<mpe_detections*>(h->dets.p), static_cast<uint32_t*>(h->hist.p), n, sp,
-                            static_cast<mpe_result*>(h->results.p), static_cast<uint32_t*>(h->corr.p), nullptr, nullptr,
-                            0.0, h->mid.p, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(out, h->results.p, (size_t)n * sizeof(mpe_result), hipMemcpyDeviceToHost, h->stream));
-  if (hist)  // (device rows are MPE_HIST_STRIDE words apart, the caller's MPE_HIST_WORDS)
-    HIP_TRY(h, hipMemcpy2DAsync(hist, MPE_HIST_WORDS * sizeof(uint32_t), h->hist.p, MPE_HIST_STRIDE * sizeof(uint32_t),
-                                MPE_HIST_WORDS * sizeof(uint32_t), (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  if (corr) HIP_TRY(h, hipMemcpyAsync(corr, h->corr.p, corr_bytes, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return MPE_OK;
+  return solve_bruteforce_impl(h, det_xy, n_det, n, markers_xyz, n_markers, K, p, out, hist, corr, 0);
 }
 
 // ---- one host process, several GPUs -----------------------------------------------------------

@@ -76,12 +76,14 @@ struct mpe_handle {
   unsigned long long relost_prev_sum = 0;
   bool relost_hot = false;              // frames were marked for the strict re-vote since the reading before
   unsigned long long fix_items_base = 0, fix_overflow_base = 0;  // cumulative counters of layouts that were replaced
-  void* mailbox = nullptr;  // pinned host memory for the single-frame tracking step (ROI in, record out)
+  void* mailbox = nullptr;  // pinned host memory for the tracked submissions (ROI slots in, records out)
   size_t mailbox_cap = 0;
-  // host-side time of the tracked frame (option "track_profile" = 1 starts / resets): sums in ns
+  // host-side time of every tracked submission (option "track_profile" = 1 starts / resets): sums in ns of pack (start
+  // of the submission to its input copy issued), enqueue (to its last command queued), wait (to its records in hand in
+  // _collect)
   int track_profile = 0;
   long long track_ns[3] = {0, 0, 0}, track_steps = 0;  // pack, enqueue, wait
-  // the lock-step submission in flight (mpe_track_abi.cpp submit_slots, for both batch submit entries), as
+  // the lock-step submission in flight (mpe_track_abi.cpp submit_slots, for every tracked entry), as
   // mpe_track_step_batch_collect needs it to repeat the set-ups whose slots overflowed the small blob tier and to hand
   // out the records: the slots are grouped by set-up (a uniform batch is one set-up), range r = slots
   // [begin, begin + count) with its set-up's parameters; slot k holds the caller's item perm[k]
@@ -99,6 +101,7 @@ struct mpe_handle {
     };
     std::vector<Range> ranges;
     std::vector<int> perm;
+    std::chrono::steady_clock::time_point t_in, t_packed, t_queued;  // option "track_profile" (t_in zero: untimed)
   } pending_track;
   // counters of the lock-step batch entries (get "track_batch_submits" / "_chains" / "_reruns"): device submissions;
   // set-ups of a submission that ran through the chain of kernels instead of the one launch (k_track_frame); set-ups
@@ -278,6 +281,8 @@ int run_pipeline(mpe_handle* h, const uint8_t* d_frames, int n_frames, const Fra
                  const SolveParams* sp, mpe_detections* d_dets, uint32_t* d_hist, mpe_result* d_results,
                  uint32_t* d_corr, const StreamHint* hint = nullptr);
 int last_kernel_ms_of_call(mpe_handle* h, float ms[5]);  // (mpe_options.cpp)
+// the text of mpe_last_error, for mpe_tracker.cpp (which sees only the C ABI and declares this itself; mpe_options.cpp)
+void set_error(mpe_handle* h, const char* what);
 }  // namespace mpe_host
 using namespace mpe_host;
 

@@ -145,6 +145,8 @@ int mpe_last_kernel_ms(mpe_handle* h, float ms[5]) {
 }
 }  // extern "C"
 namespace mpe_host {
+void set_error(mpe_handle* h, const char* what) { h->err = what; }
+
 int last_kernel_ms_of_call(mpe_handle* h, float ms[5]) {
   if (!h->have_ms) return fail(h, MPE_ERR_ARG, "profiling not enabled for the last batch");
   if (!h->prof_pipelined) {

@@ -1,13 +1,13 @@
 // mpe_track_abi.cpp — host side of libmpe_hip.so, part 3 (see mpe_host.h): one tracked frame (mpe_track_step) and the
 // lock-step time step of N camera streams (mpe_track_step_batch[_setups][_submit / _collect / _cancel]); the per-stream
-// state machine on top of them is mpe_tracker.cpp.  Both batch submit entries check their own arguments and then make
-// the same submission (submit_slots): a uniform batch is the submission of one set-up.
+// state machine on top of them is mpe_tracker.cpp.  Every entry checks its own arguments and then makes the same
+// submission (submit_slots): a uniform batch is the submission of one set-up, a tracked frame a batch of one.
 #include "mpe_host.h"
 
 extern "C" {
 
 namespace {
-const size_t kTrackHeader = 2 * MPE_MAX_MARKERS * sizeof(double);  // predicted pixels in front of the ROI
+using clk = std::chrono::steady_clock;
 
 // The records of n slots over one base pointer (device or pinned): n detection sets, n x 2*MPE_MAX_MARKERS
 // correspondence words, n results
@@ -76,87 +76,9 @@ int mpe_track_step(mpe_handle* h, const uint8_t* img, int rows, int cols, size_t
   const mpe_track_item it = {img, roi_x, roi_y, roi_w, roi_h, predicted_px};
   if (!roi_inside(it, rows, cols)) return fail(h, MPE_ERR_ARG, "ROI outside the image");
   if (h->pending_track_n) return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet (shared staging memory)");
-  ENTER(h);
-  using clk = std::chrono::steady_clock;
-  const clk::time_point t_in = h->track_profile ? clk::now() : clk::time_point();
-  clk::time_point t_packed, t_queued;
-  FrameGeom g;
-  if (make_geom(h, roi_h, roi_w, g)) return fail(h, MPE_ERR_UNSUPPORTED, "frame size unsupported");
-  DetectParams dp;
-  if (make_detect_params(p, K, D, nD, roi_x, roi_y, dp)) return fail(h, MPE_ERR_ARG, "gaussian_sigma must be in (0, 6]");
-  SolveParams sp;
-  if (make_solve_params(h, p, markers_xyz, n_markers, K, sp)) return fail(h, MPE_ERR_UNSUPPORTED, "n_markers > MPE_MAX_MARKERS");
-  const size_t roi_bytes = (size_t)g.rows * g.pitch;
-  const size_t in_bytes = kTrackHeader + roi_bytes;
-  int rc = grow_mailbox(h, in_bytes + TrackRecords::bytes(1));
-  if (rc != MPE_OK) return rc;
-  // pack [predicted pixels | ROI rows, zero padded to the pitch] into pinned memory -> one H2D copy
-  uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
-  double* pred = reinterpret_cast<double*>(mb);
-  for (int i = 0; i < 2 * MPE_MAX_MARKERS; ++i) pred[i] = i < 2 * n_markers ? predicted_px[i] : 0.0;
-  pack_roi(mb + kTrackHeader, g, it, stride_bytes);
-  const TrackRecords host_rec(mb + ((h->mailbox_cap - TrackRecords::bytes(1)) & ~(size_t)63), 1);
-  if ((rc = reserve_track(h, g, 1, in_bytes)) != MPE_OK) return rc;
-  // (Zero-copy I/O — the kernels reading the pinned mailbox over PCIe, a copy kernel writing the record back — was
-  //  built and measured in round 3: the image scan then waits for PCIe reads (4 -> 46 us for 64 streams) and the step
-  //  is no faster, 0.135 vs 0.136 ms for one stream.  The two copy commands stay.)
-  uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
-  const TrackRecords d_rec(h->track.p, 1);
-  h->have_ms = false;
-  if (h->track_profile) t_packed = clk::now();
-  HIP_TRY(h, hipMemcpyAsync(d_in, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
-  // the small blob tier alone first (a tracked ROI holds a handful of LEDs): three launches and a memset less per
-  // frame; a frame that overflows it comes back with MPE_FRAME_TOO_MANY_ROWS and is repeated through the whole chain
-  const bool optimistic = sp.n_markers >= 1 && sp.n_markers <= 8;
-  // round 6: that optimistic pass is ONE launch — scan, blob extraction, correspondences + validation, refinement as
-  // one kernel of one wave (k_track_frame): the three launch boundaries of the chain are gone (option "track_fused")
-  const bool fused = optimistic && h->track_fused;
-  if (!fused)
-    HIP_TRY(h, launch_k1a_scan(d_in + kTrackHeader, roi_bytes, static_cast<unsigned long long*>(h->flags.p), dp.thr, 0,
-                               h->stream));
-  for (int pass = optimistic ? 0 : 1; pass < 2; ++pass) {
-    if (pass == 0 && fused) {
-      const bool deliver = h->track_fused >= 2;  // the kernel stores the record to the pinned mailbox itself
-      TrackFramesArgs ta = {d_in + kTrackHeader, roi_bytes, reinterpret_cast<const double*>(d_in), nullptr,
-                            static_cast<unsigned long long*>(h->flags.p), static_cast<uint32_t*>(h->hist.p), h->mid.p,
-                            d_rec.dets, d_rec.corr, d_rec.res, deliver ? host_rec.dets : nullptr,
-                            deliver ? host_rec.corr : nullptr, deliver ? host_rec.res : nullptr, h->track_clk};
-      HIP_TRY(h, launch_track_frames(ta, 1, g, dp, sp, p->nearest_neighbour_pixel_tolerance, h->stream));
-      if (h->track_fused < 2)
-        HIP_TRY(h, hipMemcpyAsync(host_rec.dets, d_rec.dets, TrackRecords::bytes(1), hipMemcpyDeviceToHost, h->stream));
-      if (h->track_profile) t_queued = clk::now();
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-      if (h->track_clk && host_rec.dets->status != MPE_FRAME_TOO_MANY_ROWS) {
-        for (int i = 0; i < 4; ++i) h->track_clk_sum[i] += h->track_clk[i + 1] - h->track_clk[i];
-        ++h->track_clk_n;
-      }
-      if (host_rec.dets->status != MPE_FRAME_TOO_MANY_ROWS) break;
-      continue;  // (rare: the whole chain, its own scan included — the fused kernel wrote the same flag words)
-    }
-    HIP_TRY(h, launch_k1b_blobs(d_in + kTrackHeader, static_cast<unsigned long long*>(h->flags.p), 1, g, dp, d_rec.dets,
-                                static_cast<int*>(h->work.p), static_cast<uint8_t*>(h->scratch.p), h->scratch.cap, sp.n_markers, h->stream,
-                                nullptr, false, pass == 0));
-    HIP_TRY(h, launch_k3_tail(d_rec.dets, static_cast<uint32_t*>(h->hist.p), 1, sp, d_rec.res, d_rec.corr, nullptr,
-                              reinterpret_cast<const double*>(d_in), p->nearest_neighbour_pixel_tolerance, h->mid.p,
-                              h->stream));
-    HIP_TRY(h, hipMemcpyAsync(host_rec.dets, d_rec.dets, TrackRecords::bytes(1), hipMemcpyDeviceToHost, h->stream));
-    if (h->track_profile) t_queued = clk::now();
-    // (polling hipStreamQuery instead of blocking in the runtime's wait measured 133-135 against 128-129 us per frame)
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (host_rec.dets->status != MPE_FRAME_TOO_MANY_ROWS) break;
-  }
-  if (h->track_profile) {
-    const clk::time_point t_done = clk::now();
-    auto ns = [](clk::time_point a, clk::time_point b) { return (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count(); };
-    h->track_ns[0] += ns(t_in, t_packed);
-    h->track_ns[1] += ns(t_packed, t_queued);
-    h->track_ns[2] += ns(t_queued, t_done);
-    ++h->track_steps;
-  }
-  *dets_out = *host_rec.dets;
-  std::memcpy(corr_out, host_rec.corr, 2 * MPE_MAX_MARKERS * sizeof(uint32_t));
-  *out = *host_rec.res;
-  return MPE_OK;
+  // a lock-step batch of one: its slot window gives the borders and centroid offsets of the ROI
+  return mpe_track_step_batch(h, &it, 1, rows, cols, stride_bytes, p, K, D, nD, markers_xyz, n_markers, dets_out,
+                              corr_out, out);
 }
 
 namespace {
@@ -194,6 +116,7 @@ int track_range_chain(mpe_handle* h, const mpe_handle::PendingTrack::Range& r, i
 int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, const FrameGeom& g,
                  size_t stride_bytes, const TrackSetup* setups, int n_setups) {
   mpe_handle::PendingTrack& pt = h->pending_track;
+  pt.t_in = h->track_profile ? clk::now() : clk::time_point();
   auto setup_of = [item_setup](int i) { return item_setup ? item_setup[i] : 0; };
   std::vector<int> count((size_t)n_setups, 0), range_of((size_t)n_setups, -1);
   for (int i = 0; i < n; ++i) ++count[(size_t)setup_of(i)];
@@ -260,6 +183,10 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   if ((rc = reserve_track(h, g, n, in_bytes)) != MPE_OK) return rc;
   uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
   h->have_ms = false;
+  if (h->track_profile) pt.t_packed = clk::now();
+  // (Zero-copy I/O — the kernels reading the pinned mailbox over PCIe, a copy kernel writing the record back — was
+  //  built and measured in round 3: the image scan then waits for PCIe reads (4 -> 46 us for 64 streams) and the step
+  //  is no faster, 0.135 vs 0.136 ms for one stream.  The two copy commands stay.)
   HIP_TRY(h, hipMemcpyAsync(d_in, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
   pt.g = g;
   pt.slot_bytes = slot;
@@ -276,7 +203,7 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     const TrackRecords d(h->track.p, n), hr(host_rec, n);
     TrackFramesArgs ta = {pt.d_pix, slot, pt.d_pred, pt.d_wins, static_cast<unsigned long long*>(h->flags.p),
                           static_cast<uint32_t*>(h->hist.p), h->mid.p, d.dets, d.corr, d.res, deliver ? hr.dets : nullptr,
-                          deliver ? hr.corr : nullptr, deliver ? hr.res : nullptr, nullptr};
+                          deliver ? hr.corr : nullptr, deliver ? hr.res : nullptr, h->track_clk};
     const TrackSetup& su = pt.ranges[0].su;
     if (!table)
       HIP_TRY(h, launch_track_frames(ta, n_fused, g, su.dp, su.sp, su.nn_tol, h->stream));
@@ -292,6 +219,7 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     ++h->track_batch_chains;
   }
   if (n_fused < n || !deliver) HIP_TRY(h, hipMemcpyAsync(host_rec, h->track.p, rec_bytes, hipMemcpyDeviceToHost, h->stream));
+  if (h->track_profile) pt.t_queued = clk::now();
   h->pending_track_n = n;
   h->pending_track_rec = host_rec;
   return MPE_OK;
@@ -383,9 +311,15 @@ int mpe_track_step_batch_collect(mpe_handle* h, mpe_detections* dets_out, uint32
   h->pending_track_n = 0;
   h->pending_track_rec = nullptr;
   ENTER(h);
+  // (polling hipStreamQuery instead of blocking in the runtime's wait measured 133-135 against 128-129 us per frame)
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   const mpe_handle::PendingTrack& pt = h->pending_track;
   const TrackRecords rec(host_rec, n);
+  // option "track_phase_clocks": the stamps of block 0 = slot 0, unless that frame is repeated below
+  if (h->track_clk && pt.ranges[0].fused && rec.dets[0].status != MPE_FRAME_TOO_MANY_ROWS) {
+    for (int i = 0; i < 4; ++i) h->track_clk_sum[i] += h->track_clk[i + 1] - h->track_clk[i];
+    ++h->track_clk_n;
+  }
   // a slot that overflowed the small blob tier: its set-up's range again, through every tier (the inputs are still on
   // the device: nothing has been submitted on this handle since)
   bool again = false;
@@ -402,6 +336,13 @@ int mpe_track_step_batch_collect(mpe_handle* h, mpe_detections* dets_out, uint32
   if (again) {
     HIP_TRY(h, hipMemcpyAsync(host_rec, h->track.p, pt.rec_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
+  if (h->track_profile && pt.t_in != clk::time_point()) {  // (a submission made before the option was set: untimed)
+    auto ns = [](clk::time_point a, clk::time_point b) { return (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count(); };
+    h->track_ns[0] += ns(pt.t_in, pt.t_packed);
+    h->track_ns[1] += ns(pt.t_packed, pt.t_queued);
+    h->track_ns[2] += ns(pt.t_queued, clk::now());
+    ++h->track_steps;
   }
   // slot k holds item k (always so with one set-up): one copy per array — slot by slot, a time step of 64 uniform streams
   // measured 5 us longer

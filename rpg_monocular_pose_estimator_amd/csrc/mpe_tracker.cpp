@@ -1,7 +1,9 @@
 // mpe_tracker.cpp — the stateful PoseEstimator state machine (tracking path) on top of the HIP
 // stages.  Host side only: a few 4x4 / 6-vector operations per frame; all image and pose compute
-// runs in the kernels through the public C ABI (mpe_find_leds with a ROI, mpe_check_and_refine,
-// mpe_solve_bruteforce).
+// runs in the kernels through the public C ABI.  One state machine (BatchCtx) serves one stream and
+// N streams in lock step alike: its device steps are the lock-step submissions
+// (mpe_track_step_batch_setups_submit / _collect: detection in the ROI with correspondences,
+// validation and refinement) and mpe_solve_bruteforce_batch (re-initialisation).
 //
 // Reference: PoseEstimator::estimateBodyPose (pose_estimator.cpp:62-147), predictPose (:232-244),
 // predictMarkerPositionsInImage (:270-276), findCorrespondences (:372-392), updatePose /
@@ -16,6 +18,10 @@
 #include <vector>
 
 #include "../../include/mpe.h"
+
+namespace mpe_host {
+void set_error(mpe_handle* h, const char* what);  // the text of mpe_last_error (mpe_options.cpp)
+}
 
 namespace {
 
@@ -192,6 +198,7 @@ int find_correspondences(const double* pred_px, int n_markers, const double* det
   return nc;
 }
 
+struct BatchCtx;
 }  // namespace
 
 struct mpe_tracker {
@@ -212,11 +219,8 @@ struct mpe_tracker {
   std::vector<uint32_t> corr;        // rows (marker, detection)
   int n_corr = 0, gn_iterations = 0;
   bool used_bruteforce = false;
-  // result of the speculative nearest-neighbour + refine pass that mpe_track_step ran together with
-  // the detection; only meaningful while fused_valid (>= 4 fresh detections)
-  bool fused_valid = false;
-  mpe_result fused_res;
-  uint32_t fused_corr[2 * MPE_MAX_MARKERS];
+  BatchCtx* solo = nullptr;  // mpe_tracker_estimate's lock-step group of one, kept for its buffers
+  ~mpe_tracker();
 };
 
 namespace {
@@ -278,34 +282,6 @@ void determine_roi(mpe_tracker* t, int rows, int cols) {
                      t->D.empty() ? nullptr : t->D.data(), (int)t->D.size(), t->roi);
 }
 
-int detect(mpe_tracker* t, const uint8_t* img, int rows, int cols, size_t stride) {
-  double und[2 * MPE_MAX_DETECTIONS];
-  float dist[2 * MPE_MAX_DETECTIONS];
-  int n = 0;
-  int rc = mpe_find_leds(t->h, img, rows, cols, stride, t->roi[0], t->roi[1], t->roi[2], t->roi[3], &t->p, t->K,
-                         t->D.empty() ? nullptr : t->D.data(), (int)t->D.size(), und, dist, MPE_MAX_DETECTIONS, &n);
-  if (rc != MPE_OK) return rc;
-  t->det_dist.assign(dist, dist + 2 * n);
-  if (n > 0) t->det.assign(und, und + 2 * n);  // pixel_positions is only rewritten when something was found
-  return MPE_OK;
-}
-
-// Tracking branch: detection in the ROI and, in the same device submission, the nearest-neighbour
-// correspondences + validation + refinement the reference would run next if >= 4 LEDs are found.
-int detect_and_try(mpe_tracker* t, const uint8_t* img, int rows, int cols, size_t stride) {
-  mpe_detections d;
-  t->fused_valid = false;
-  int rc = mpe_track_step(t->h, img, rows, cols, stride, t->roi[0], t->roi[1], t->roi[2], t->roi[3], &t->p, t->K,
-                          t->D.empty() ? nullptr : t->D.data(), (int)t->D.size(), t->markers.data(), n_markers(t),
-                          t->predicted_px.data(), &d, t->fused_corr, &t->fused_res);
-  if (rc != MPE_OK) return rc;
-  if (d.status != 0) return d.status;
-  t->det_dist.assign(d.dist_xy, d.dist_xy + 2 * d.n);
-  if (d.n > 0) t->det.assign(d.undist_xy, d.undist_xy + 2 * d.n);  // as in detect(): kept when nothing was found
-  t->fused_valid = d.n >= 4;
-  return MPE_OK;
-}
-
 void take_result(mpe_tracker* t, const mpe_result& r) {
   std::memcpy(t->predicted.a, r.T, sizeof(r.T));
   std::memcpy(t->cov, r.cov, sizeof(r.cov));
@@ -317,59 +293,6 @@ void take_result(mpe_tracker* t, const mpe_result& r) {
   t->t_previous = t->t_current;
   t->t_current = t->t_predicted;
   t->pose_updated = true;
-}
-
-int bruteforce(mpe_tracker* t) {  // initialise() + optimiseAndUpdatePose()
-  mpe_result r;
-  std::vector<uint32_t> c(2 * MPE_MAX_MARKERS, 0);
-  const int nd = (int)t->det.size() / 2, nm = n_markers(t);
-  std::vector<uint32_t> hist((size_t)std::max(1, nd * nm), 0);
-  t->used_bruteforce = true;
-  int rc = mpe_solve_bruteforce(t->h, t->det.data(), nd, t->markers.data(), nm, t->K, &t->p, &r, hist.data(), c.data());
-  if (rc != MPE_OK) return rc;
-  if (r.status < 0) return r.status;
-  // initialise() only assigns correspondences_ when the histogram holds a vote (pose_estimator.cpp:704-719);
-  // with an all-zero histogram the member keeps its previous rows
-  bool any_vote = false;
-  for (uint32_t v : hist) any_vote |= (v != 0);
-  if (any_vote) {
-    t->n_corr = r.n_corr;
-    t->corr.assign(c.begin(), c.begin() + 2 * r.n_corr);
-  }
-  if (r.status == MPE_FRAME_POSE) take_result(t, r);
-  return MPE_OK;
-}
-
-// findCorrespondencesAndPredictPose (pose_estimator.cpp:831-848)
-int track(mpe_tracker* t) {
-  if (t->fused_valid) {  // already done on the device together with the detection
-    t->fused_valid = false;
-    const mpe_result& r = t->fused_res;
-    if (r.status < 0) return r.status;
-    t->n_corr = r.n_corr;
-    t->corr.assign(t->fused_corr, t->fused_corr + 2 * r.n_corr);
-    if (r.status == MPE_FRAME_POSE) {
-      take_result(t, r);
-      return MPE_OK;
-    }
-    return bruteforce(t);
-  }
-  const int nm = n_markers(t), nd = (int)t->det.size() / 2;
-  t->corr.assign(2 * (size_t)nm, 0u);
-  const int nc = find_correspondences(t->predicted_px.data(), nm, t->det.data(), nd,
-                                      t->p.nearest_neighbour_pixel_tolerance, t->corr.data());
-  t->corr.resize(2 * (size_t)nc);
-  t->n_corr = (int)t->corr.size() / 2;
-  mpe_result r;
-  int rc = mpe_check_and_refine(t->h, t->det.data(), nd, t->markers.data(), nm, t->K, &t->p, t->corr.data(), t->n_corr,
-                                &r);
-  if (rc != MPE_OK) return rc;
-  if (r.status < 0) return r.status;
-  if (r.status == MPE_FRAME_POSE) {
-    take_result(t, r);
-    return MPE_OK;
-  }
-  return bruteforce(t);  // reinitialise if the correspondences were not valid
 }
 
 }  // namespace
@@ -529,75 +452,11 @@ int mpe_tracker_get_distorted_centers(mpe_tracker* t, float* xy, int cap_points)
   return (int)t->det_dist.size() / 2;
 }
 
-int mpe_tracker_estimate(mpe_tracker* t, const uint8_t* img, int rows, int cols, size_t stride_bytes, double time,
-                         mpe_result* out, int info[8]) {
-  if (!t || !img) return MPE_ERR_ARG;
-  t->pose_updated = false;
-  t->used_bruteforce = false;
-  t->det.clear();
-  // correspondences_ is a member of the reference object: it keeps its last value when a frame has
-  // too few detections (getCorrespondences() then returns the stale rows) — same here
-  int rc = MPE_OK;
-  if (t->it_since_initialized < 1) {  // pose_estimator.cpp:68-96
-    t->t_predicted = time;
-    t->roi[0] = t->roi[1] = 0;
-    t->roi[2] = cols;
-    t->roi[3] = rows;
-    if ((rc = detect(t, img, rows, cols, stride_bytes)) != MPE_OK) return rc;
-    if (t->det.size() / 2 >= 4)
-      if ((rc = bruteforce(t)) != MPE_OK) return rc;
-  } else {  // pose_estimator.cpp:98-144
-    // predictWithROI (:814-829)
-    if (t->it_since_initialized >= 2) {
-      // predictPose (:232-244)
-      t->t_predicted = time;
-      t->predicted = predict_pose(t->current, t->previous, t->t_current, t->t_previous, t->t_predicted);
-    } else {
-      t->t_predicted = time;
-    }
-    for (int i = 0; i < n_markers(t); ++i)
-      project(t, t->predicted, &t->markers[3 * i], t->predicted_px[2 * i], t->predicted_px[2 * i + 1]);
-    determine_roi(t, rows, cols);
-    if ((rc = detect_and_try(t, img, rows, cols, stride_bytes)) != MPE_OK) return rc;
-    bool repeat_check = true;
-    unsigned num_loops = 0;
-    do {
-      num_loops++;
-      if (t->det.size() / 2 >= 4) {
-        if ((rc = track(t)) != MPE_OK) return rc;
-        repeat_check = false;
-      } else if (num_loops < 2) {  // too few LEDs in the ROI: search the whole image once
-        t->roi[0] = t->roi[1] = 0;
-        t->roi[2] = cols;
-        t->roi[3] = rows;
-        if ((rc = detect_and_try(t, img, rows, cols, stride_bytes)) != MPE_OK) return rc;
-      } else {
-        repeat_check = false;
-      }
-    } while (repeat_check);
-  }
-  if (out) {
-    std::memcpy(out->T, t->predicted.a, sizeof(out->T));
-    std::memcpy(out->cov, t->cov, sizeof(out->cov));
-    out->status = t->pose_updated ? MPE_FRAME_POSE : MPE_FRAME_NO_POSE;
-    out->n_det = (int)t->det.size() / 2;
-    out->n_corr = t->n_corr;
-    out->gn_iterations = t->gn_iterations;
-  }
-  if (info) {
-    for (int i = 0; i < 4; ++i) info[i] = t->roi[i];
-    info[4] = (int)t->it_since_initialized;
-    info[5] = (int)t->det.size() / 2;
-    info[6] = t->n_corr;
-    info[7] = t->used_bruteforce ? 1 : 0;
-  }
-  return t->pose_updated ? 1 : 0;
-}
-
 // ---- N trackers in lock step -----------------------------------------------------------------------
-// The state machine of mpe_tracker_estimate per stream, with the device steps of all streams that are at the same
+// The state machine of estimateBodyPose per stream, with the device steps of all streams that are at the same
 // point batched into one submission: DETECT = findLeds in the stream's ROI (+ nearest-neighbour correspondences,
 // validation and refinement when tracking), BRUTE = initialise() + optimisePose on the stream's detections.
+// A single stream (mpe_tracker_estimate, mpe_tracker_run_sequence) is a group of one.
 // A frame is processed in three parts so that a caller can overlap the host work of one group of streams with the
 // device work of another: begin (per-stream prediction / ROI), the first DETECT submission (asynchronous), and
 // finish (collect it, then whatever else the streams need — second size class, whole-image retries,
@@ -680,8 +539,9 @@ struct BatchCtx {
       L[(size_t)i] = BatchLane();
       t->pose_updated = false;
       t->used_bruteforce = false;
+      // (correspondences_ is a member of the reference object: it keeps its last value when a frame has too few
+      //  detections, getCorrespondences() then returns the stale rows — same here)
       t->det.clear();
-      t->fused_valid = false;
       t->t_predicted = times[i];
       if (t->it_since_initialized < 1) {
         t->roi[0] = t->roi[1] = 0;
@@ -838,10 +698,12 @@ struct BatchCtx {
     return MPE_OK;
   }
 
-  // error path: abandon whatever this group has in flight, so that its handle accepts the next submission
+  // error path: abandon this group's submission if one is in flight, so that its handle accepts the next one (a
+  // submission this group did not make — the one that got a call on a busy handle refused — is left alone)
   void cancel() {
+    if (pend.empty()) return;
     pend.clear();
-    if (h) (void)mpe_track_step_batch_cancel(h);
+    (void)mpe_track_step_batch_cancel(h);
   }
 
   // first asynchronous submission of a frame: the size class that has lanes (the small one first)
@@ -913,6 +775,8 @@ struct BatchCtx {
 };
 }  // namespace
 
+mpe_tracker::~mpe_tracker() { delete solo; }
+
 extern "C" {
 
 static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
@@ -930,6 +794,26 @@ static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* i
     return rc;
   }
   return c.outputs(out, 1, info, 8, updated);
+}
+
+// one stream: a lock-step group of one
+int mpe_tracker_estimate(mpe_tracker* t, const uint8_t* img, int rows, int cols, size_t stride_bytes, double time,
+                         mpe_result* out, int info[8]) {
+  if (!t || !img) return MPE_ERR_ARG;
+  if (!t->solo) t->solo = new BatchCtx();
+  BatchCtx& c = *t->solo;
+  int rc = c.validate(&t, 1);
+  if (rc != MPE_OK) return rc;
+  c.begin(&img, rows, cols, stride_bytes, &time);
+  if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
+    c.cancel();
+    return rc;
+  }
+  if (c.L[0].error) {  // a device capacity was exceeded on this frame: its code, out / info untouched
+    mpe_host::set_error(t->h, "frame exceeded a device capacity");
+    return c.L[0].error;
+  }
+  return c.outputs(out, 1, info, 8, nullptr);
 }
 
 int mpe_tracker_estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
@@ -1066,26 +950,14 @@ int mpe_tracker_run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t
                                                  times, out, info, 1);
 }
 
+// one stream's sequence: the lock-step loop over a group of one (a frame that exceeds a device capacity gets a zeroed
+// record that carries the code, and the sequence goes on)
 int mpe_tracker_run_sequence(mpe_tracker* t, const uint8_t* frames, int n_frames, int rows, int cols,
                              size_t stride_bytes, size_t frame_stride_bytes, const double* times, mpe_result* out,
                              int* info) {
   if (!t || !frames || !times || n_frames < 0) return MPE_ERR_ARG;
-  int updated = 0;
-  for (int f = 0; f < n_frames; ++f) {
-    const int rc = mpe_tracker_estimate(t, frames + (size_t)f * frame_stride_bytes, rows, cols, stride_bytes, times[f],
-                                        out ? out + f : nullptr, info ? info + 8 * f : nullptr);
-    if (rc <= MPE_FRAME_TOO_MANY_DETECTIONS) {  // this frame exceeded a device capacity: recorded, the sequence goes on
-      if (out) {
-        std::memset(&out[f], 0, sizeof(mpe_result));
-        out[f].status = rc;
-      }
-      if (info) std::memset(info + 8 * f, 0, 8 * sizeof(int));
-      continue;
-    }
-    if (rc < 0) return rc;  // usage / HIP error
-    updated += rc;
-  }
-  return updated;
+  return run_sequences_batch(&t, 1, &frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info, 1,
+                             false);
 }
 
 }  // extern "C"

@@ -460,7 +460,8 @@ def test_capacity_overrun_is_reported_alike_by_single_and_batch_replays(orc):
     """A frame with more blobs than MPE_MAX_DETECTIONS in the middle of a sequence: mpe_tracker_run_sequence and the
     lock-step batch replay both hand out a ZEROED record that carries the status code for that frame (and a zeroed
     info row), and both carry on with the sequence; a collect without a submission and a failed batch leave the
-    handle usable."""
+    handle usable.  The lone tracker runs as a lock-step group of one: its frames are counted as
+    lock-step submissions and feed the host timers and phase clocks of the tracked frame."""
     seq = synth.make_sequence("C2", 8, seed=61)
     frames = seq["frames"].copy()
     rng = np.random.default_rng(8)
@@ -472,8 +473,14 @@ def test_capacity_overrun_is_reported_alike_by_single_and_batch_replays(orc):
     P = mpe.demo_params()
     h1, h2 = mpe.Handle(), mpe.Handle()
     try:
+        h1.set_option("track_profile", 1)
+        h1.set_option("track_phase_clocks", 1)
+        submits0 = h1.get_option("track_batch_submits")
         t1 = mpe.Tracker(h1, seq["markers"], seq["K"], seq["D"], P)
         rec1, info1 = t1.run_sequence(frames, times)
+        assert h1.get_option("track_batch_submits") - submits0 >= len(frames)  # (at least one submission per frame)
+        assert h1.get_option("track_steps") >= len(frames) and h1.get_option("track_ns_wait") > 0
+        assert all(h1.get_option("track_phase_cycles_%d" % i) > 0 for i in range(4))
         t2 = mpe.Tracker(h2, seq["markers"], seq["K"], seq["D"], P)
         rec2, info2 = mpe.tracker_run_sequences_batch([t2], [frames], times)
         rec2, info2 = rec2[0], info2[0]

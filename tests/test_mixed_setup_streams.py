@@ -298,6 +298,7 @@ def test_submit_entries_refuse_bad_usage_and_stay_usable():
     x1, y1 = min(cols, int(px[:, 0].max()) + 40), min(rows, int(px[:, 1].max()) + 40)
     h = mpe.Handle(0)
     hp = h._h
+    trackers = []
 
     def items(roi_x=0):
         it = (_TrackItem * 2)()
@@ -350,8 +351,28 @@ def test_submit_entries_refuse_bad_usage_and_stay_usable():
             assert collect() == ref
             assert entry(items()) == 0 and collect() == ref
         assert h.get_option("track_batch_submits") == n0 + 4
+        # while a submission is pending, a tracked frame, a lone tracker on either branch and a lock-step call are
+        # refused, and none of them touches that submission
+        trackers += [mpe.Tracker(h, markers, K, D, P), mpe.Tracker(h, markers, K, D, P)]
+        fresh, tracking = trackers
+        assert tracking.estimate(img, 0.0)["it_since_initialized"] >= 1
+        # (that frame was a submission of one slot: the bytes of a record beyond its valid entries are what the device
+        #  buffer last held there, so the reference records are taken again)
+        assert submit(items()) == 0
+        ref = collect()
+        calls = [("mpe_track_step", lambda: h.track_step(img, (x0, y0, x1 - x0, y1 - y0), P, K, D, markers, pred)),
+                 ("uninitialised tracker", lambda: fresh.estimate(img, 0.1)),
+                 ("tracking tracker", lambda: tracking.estimate(img, 0.1)),
+                 ("mpe_tracker_estimate_batch", lambda: mpe.tracker_estimate_batch(trackers, [img, img], [0.1, 0.1]))]
+        for what, call in calls:
+            assert submit(items()) == 0
+            with pytest.raises(mpe.MpeError, match=r"\(-1\): a submitted batch has not been collected yet"):
+                call()
+            assert collect() == ref, what
     finally:
         lib.mpe_track_step_batch_cancel(hp)
+        for t in trackers:
+            t.close()
         h.close()
 
 
