@@ -320,7 +320,7 @@ int mpe_track_step(mpe_handle* h, const uint8_t* img, int rows, int cols, size_t
  * item = detection only (out[i].status = 1).  Group items of very different ROI size into separate calls:
  * the slot is as large as the largest ROI of the call.  dets_out n, corr_out n x 2*MPE_MAX_MARKERS, out n. */
 typedef struct mpe_track_item {
-  const uint8_t* img;          /* HOST image of this stream */
+  const uint8_t* img;          /* HOST image of this stream (a DEVICE pointer in the *_device entries below) */
   int roi_x, roi_y, roi_w, roi_h;
   const double* predicted_px;  /* n_markers x 2 undistorted pixels, or NULL */
 } mpe_track_item;
@@ -363,6 +363,25 @@ int mpe_track_step_batch_setups(mpe_handle* h, const mpe_track_item* items, cons
 int mpe_track_step_batch_setups_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
                                        int rows, int cols, size_t stride_bytes, const mpe_track_setup* setups,
                                        int n_setups);
+/* mpe_track_step_batch_setups[_submit] for streams whose frames are already in DEVICE memory (a decoder, a simulator,
+ * a replay buffer, mpe_convert_to_mono8 with a device destination): items[i].img is a device pointer here, the struct
+ * is unchanged.  Instead of cloning every ROI on the host and copying the pixels (what the entries above do), the
+ * submission copies only its small header and a kernel gathers the ROIs from the caller's images into the same slots,
+ * byte for byte; everything behind that is the same submission, so the records are byte-identical to those of
+ * mpe_track_step_batch_setups over the same frames in host memory, and mpe_track_step_batch_collect / _cancel serve
+ * this submit too.  item_setup == NULL with n_setups == 1 is a uniform batch (there is no separate uniform entry).
+ * Every img must lie, with its whole image (to the last pixel of row rows - 1), inside one device allocation on the
+ * handle's device: host memory — pinned memory included — is refused with MPE_ERR_ARG before anything is submitted
+ * (the host entries are for that); the other usage errors are those of mpe_track_step_batch_setups_submit.
+ * Ordering: the gather runs on the handle's stream.  The frames must be final in that stream's order when _submit is
+ * called (as with mpe_estimate_batch_device) and must stay unmodified until _collect / _cancel has returned: a slot
+ * that overflows the small blob tier is re-run from the gathered slots, but a retry by the caller reads them again. */
+int mpe_track_step_batch_setups_device(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                                       int rows, int cols, size_t stride_bytes, const mpe_track_setup* setups,
+                                       int n_setups, mpe_detections* dets_out, uint32_t* corr_out, mpe_result* out);
+int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                                              int rows, int cols, size_t stride_bytes, const mpe_track_setup* setups,
+                                              int n_setups);
 /* mpe_solve_bruteforce for N detection sets in one submission (the re-initialisations of a lock-step batch):
  * det_xy n x MPE_MAX_DETECTIONS x 2 (n_det[i] valid rows); hist (optional) n x MPE_MAX_DETECTIONS x
  * MPE_MAX_MARKERS, corr (optional) n x 2*MPE_MAX_MARKERS. */
@@ -435,6 +454,22 @@ int mpe_tracker_run_sequences_batch_mixed_threads(mpe_tracker* const* trackers, 
                                                   int n_frames, int rows, int cols, size_t stride_bytes,
                                                   size_t frame_stride_bytes, const double* times, mpe_result* out,
                                                   int* info, int n_threads);
+
+/* mpe_tracker_estimate_batch_mixed / mpe_tracker_run_sequences_batch_mixed_threads for frames in DEVICE memory:
+ * d_imgs / d_frames are HOST arrays of device pointers (d_imgs[i] stream i's frame, d_frames[i] stream i's sequence),
+ * on the device of the trackers' handle.  The ROI and whole-image detections go through
+ * mpe_track_step_batch_setups_device_submit instead of the host-frame submission — no frame and no ROI crosses PCIe —,
+ * the re-initialisations through mpe_solve_bruteforce_batch on detections that are on the host anyway.  The trackers
+ * may mix set-ups (the _mixed rules: distinct trackers, one handle per group).  Records and info are byte-identical to
+ * those of the host-frame entries over the same frames.  Ordering as for mpe_track_step_batch_setups_device: the
+ * frames are final in the order of the handle's stream at the call and unmodified until it returns. */
+int mpe_tracker_estimate_batch_device(mpe_tracker* const* trackers, int n, const uint8_t* const* d_imgs, int rows,
+                                      int cols, size_t stride_bytes, const double* times, mpe_result* out, int* info,
+                                      int* updated);
+int mpe_tracker_run_sequences_batch_device_threads(mpe_tracker* const* trackers, int n, const uint8_t* const* d_frames,
+                                                   int n_frames, int rows, int cols, size_t stride_bytes,
+                                                   size_t frame_stride_bytes, const double* times, mpe_result* out,
+                                                   int* info, int n_threads);
 
 /* The estimator's private state (pose_estimator.h:56-62, 74-79), for callers that drive the public
  * step methods of the class (predictPose, findCorrespondences, ... — see compat/) between calls of

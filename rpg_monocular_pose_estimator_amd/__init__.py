@@ -10,7 +10,8 @@ from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYP
                       predict_pose, project_points, find_correspondences, shard_bounds, estimate_batch_multi,
                       estimate_batch_multi_device_gather, ENCODINGS,
                       tracker_estimate_batch, tracker_run_sequences_batch, tracker_estimate_batch_mixed,
-                      tracker_run_sequences_batch_mixed, PinnedFrames)
+                      tracker_run_sequences_batch_mixed, PinnedFrames, tracker_estimate_batch_device,
+                      tracker_run_sequences_batch_device)
 from .pose_estimator import PoseEstimator  # noqa: F401
 
 __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE", "DETECTIONS_DTYPE",
@@ -18,4 +19,5 @@ __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE"
            "demo_params", "exported_symbols", "source_fingerprint", "device_source", "DEVICE_SOURCES", "PoseEstimator", "Tracker", "determine_roi", "distort_points",
            "exponential_map", "logarithm_map", "predict_pose", "project_points", "find_correspondences",
            "shard_bounds", "estimate_batch_multi", "estimate_batch_multi_device_gather", "ENCODINGS", "tracker_estimate_batch", "tracker_run_sequences_batch", "tracker_estimate_batch_mixed",
-           "tracker_run_sequences_batch_mixed", "PinnedFrames"]
+           "tracker_run_sequences_batch_mixed", "PinnedFrames", "tracker_estimate_batch_device",
+           "tracker_run_sequences_batch_device"]

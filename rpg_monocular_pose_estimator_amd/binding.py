@@ -196,6 +196,11 @@ def load_library():
                                                             C.c_size_t, dp, C.c_void_p, C.c_void_p, C.c_int]
     lib.mpe_tracker_estimate_batch_mixed.argtypes = lib.mpe_tracker_estimate_batch.argtypes
     lib.mpe_tracker_run_sequences_batch_mixed_threads.argtypes = lib.mpe_tracker_run_sequences_batch_threads.argtypes
+    lib.mpe_tracker_estimate_batch_device.argtypes = lib.mpe_tracker_estimate_batch.argtypes
+    lib.mpe_tracker_run_sequences_batch_device_threads.argtypes = lib.mpe_tracker_run_sequences_batch_threads.argtypes
+    lib.mpe_track_step_batch_setups_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                                       C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mpe_track_step_batch_setups_device_submit.argtypes = lib.mpe_track_step_batch_setups_device.argtypes[:9]
     lib.mpe_shard_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mpe_shard_bounds.restype = None
     lib.mpe_estimate_batch_multi.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
@@ -264,6 +269,78 @@ def tracker_run_sequences_batch_mixed(trackers, frames, times, threads=1):
     """mpe_tracker_run_sequences_batch_mixed_threads: as tracker_run_sequences_batch, each handle's trackers one
     lock-step group that may mix cameras, marker sets and parameters."""
     return tracker_run_sequences_batch(trackers, frames, times, threads, mixed=True)
+
+
+def _device_images(imgs, lead):
+    """The streams' images in device memory: a list of torch uint8 CUDA tensors, one per stream, or one tensor with a
+    leading stream dimension; `lead` dimensions in front of (rows, cols).  All on one device, pixels contiguous within
+    a row, the same strides.  Work queued on torch's current stream of that device is waited for (the frames must be
+    final when they are submitted).  -> (the tensors — keep them alive across the call —, device pointers, shape,
+    strides in bytes)."""
+    import torch
+    ts = list(imgs.unbind(0)) if _is_torch(imgs) else list(imgs)
+    t0 = ts[0]
+    for t in ts:
+        if not (_is_torch(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == lead + 2 and t.stride(-1) == 1):
+            raise MpeError("device frames: torch uint8 CUDA tensors with contiguous rows are needed (host frames: the host entries)")
+        if t.shape != t0.shape or t.stride() != t0.stride() or t.device != t0.device:
+            raise MpeError("device frames: every stream needs the same shape, strides and device")
+    torch.cuda.current_stream(t0.device).synchronize()
+    return ts, (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), tuple(t0.shape), tuple(t0.stride())
+
+
+def tracker_estimate_batch_device(trackers, imgs, times):
+    """mpe_tracker_estimate_batch_device: tracker_estimate_batch[_mixed] for frames that are in device memory — imgs: a
+    list of (rows, cols) torch uint8 CUDA tensors, one per tracker, or one (N, rows, cols) tensor, on the device of the
+    trackers' handle.  The trackers may mix set-ups.  -> (records (N), info (N,8), updated (N) bool), those of the host
+    entries over the same frames."""
+    lib = load_library()
+    n = len(trackers)
+    keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0)
+    assert len(keep) == n
+    ts = (C.c_void_p * n)(*[t._t for t in trackers])
+    times = _f64(times).reshape(-1)
+    rec = np.zeros(n, RESULT_DTYPE)
+    info = np.zeros((n, 8), np.int32)
+    upd = np.zeros(n, np.int32)
+    rc = lib.mpe_tracker_estimate_batch_device(ts, n, ptrs, rows, cols, stride, _dp(times), rec.ctypes.data,
+                                               info.ctypes.data, upd.ctypes.data)
+    del keep
+    if rc < 0:
+        raise MpeError("mpe_tracker_estimate_batch_device failed (%d): %s"
+                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
+    return rec, info, upd.astype(bool)
+
+
+def tracker_run_sequences_batch_device(trackers, frames, times, threads=1):
+    """mpe_tracker_run_sequences_batch_device_threads: tracker_run_sequences_batch[_mixed] over sequences that are in
+    device memory — frames: a list of (n, rows, cols) torch uint8 CUDA tensors, one per tracker, or one (N, n, rows, cols)
+    tensor.  Each handle's trackers form one lock-step group that may mix set-ups.  -> (records (N,n), info (N,n,8))."""
+    lib = load_library()
+    N = len(trackers)
+    keep, ptrs, (n, rows, cols), (fstride, stride, _) = _device_images(frames, 1)
+    assert len(keep) == N
+    ts = (C.c_void_p * N)(*[t._t for t in trackers])
+    times = _f64(times).reshape(-1)
+    rec = np.zeros((N, n), RESULT_DTYPE)
+    info = np.zeros((N, n, 8), np.int32)
+    rc = lib.mpe_tracker_run_sequences_batch_device_threads(ts, N, ptrs, n, rows, cols, stride, fstride, _dp(times),
+                                                            rec.ctypes.data, info.ctypes.data, int(threads))
+    del keep
+    if rc < 0:
+        raise MpeError("mpe_tracker_run_sequences_batch_device_threads failed (%d): %s"
+                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
+    return rec, info
+
+
+class TrackItem(C.Structure):  # mpe_track_item
+    _fields_ = [("img", C.c_void_p), ("roi_x", C.c_int), ("roi_y", C.c_int), ("roi_w", C.c_int), ("roi_h", C.c_int),
+                ("predicted_px", C.c_void_p)]
+
+
+class TrackSetup(C.Structure):  # mpe_track_setup
+    _fields_ = [("p", C.c_void_p), ("K", C.c_void_p), ("D", C.c_void_p), ("nD", C.c_int), ("markers_xyz", C.c_void_p),
+                ("n_markers", C.c_int)]
 
 
 class PinnedFrames:
@@ -599,6 +676,51 @@ class Handle:
         return dict(status=res.status, T=np.array(res.T).reshape(4, 4), cov=np.array(res.cov).reshape(6, 6),
                     n_corr=res.n_corr, corr=corr[:max(res.n_corr, 0)].copy(), det_status=det.status,
                     undist=np.array(det.undist_xy[:2 * n]).reshape(-1, 2), gn_iterations=res.gn_iterations)
+
+    # ---- one lock-step time step of N streams: mpe_track_step_batch_setups[_device] ----------------------
+    def _track_step_batch(self, entry, ptrs, rows, cols, stride, rois, predicted_px, setups, item_setup):
+        n = len(ptrs)
+        keep = []
+        su = (TrackSetup * len(setups))()
+        for s, (markers, K, D, params) in enumerate(setups):
+            markers, K, D = _f64(markers).reshape(-1, 3), _f64(K).reshape(9), _f64(D).reshape(-1)
+            keep += [markers, K, D, params]
+            su[s] = TrackSetup(C.addressof(params), K.ctypes.data, D.ctypes.data if len(D) else None, len(D),
+                               markers.ctypes.data, len(markers))
+        items = (TrackItem * n)()
+        for i in range(n):
+            pred = None if predicted_px[i] is None else _f64(predicted_px[i]).reshape(-1, 2)
+            keep.append(pred)
+            items[i] = TrackItem(ptrs[i], *[int(v) for v in rois[i]], None if pred is None else pred.ctypes.data)
+        idx = None if item_setup is None else (C.c_int * n)(*[int(v) for v in item_setup])
+        dets, corr = np.zeros(n, DETECTIONS_DTYPE), np.zeros((n, MAX_MARKERS, 2), np.uint32)
+        res = np.zeros(n, RESULT_DTYPE)
+        rc = getattr(self._lib, entry)(self._h, items, idx, n, rows, cols, C.c_size_t(stride), su, len(setups),
+                                       C.c_void_p(dets.ctypes.data), C.c_void_p(corr.ctypes.data),
+                                       C.c_void_p(res.ctypes.data))
+        self._check(rc, entry)
+        return dets, corr, res
+
+    def track_step_batch(self, imgs, rois, predicted_px, setups, item_setup):
+        """mpe_track_step_batch_setups: one time step of N streams, frames on the host.  imgs: N (rows, cols) uint8
+        arrays of one shape and row stride; rois: N x (x, y, w, h); predicted_px: per stream (n_markers, 2) or None
+        (detection only); setups: list of (markers, K, D, params); item_setup: the set-up of every stream.
+        -> (detections [DETECTIONS_DTYPE] (N), correspondences (N, MAX_MARKERS, 2) uint32, records [RESULT_DTYPE] (N))."""
+        rows, cols = imgs[0].shape
+        stride = imgs[0].strides[0]
+        assert all(im.dtype == np.uint8 and im.shape == (rows, cols) and im.strides == (stride, 1) for im in imgs)
+        return self._track_step_batch("mpe_track_step_batch_setups", [im.ctypes.data for im in imgs], rows, cols, stride,
+                                      rois, predicted_px, setups, item_setup)
+
+    def track_step_batch_device(self, imgs, rois, predicted_px, setups, item_setup=None):
+        """mpe_track_step_batch_setups_device: track_step_batch for frames in device memory.  imgs: a list of N
+        (rows, cols) torch uint8 CUDA tensors on this handle's device (any common row stride), or one (N, rows, cols)
+        tensor; item_setup None: one set-up for all.  Same records as track_step_batch over the same frames."""
+        keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0)
+        out = self._track_step_batch("mpe_track_step_batch_setups_device", list(ptrs), rows, cols, stride, rois,
+                                     predicted_px, setups, item_setup)
+        del keep
+        return out
 
     # ---- static primitives, batched ----------------------------------------------------------------
     def p3p_batch(self, fv, wp):

@@ -1,0 +1,81 @@
+// mpe_gather.h — one 16-byte segment of a ROI slot, read from an image of arbitrary base, stride and ROI origin: the
+// arithmetic of k_gather_rois (mpe_track_device.hip), in a header of its own so that the CPU tier compiles it for the
+// host (tests/host/gather_host.cpp) and runs it under AddressSanitizer.
+//
+// A slot is what pack_roi (mpe_track_abi.cpp) writes on the host: row r < roi_h holds the roi_w bytes of image row
+// roi_y + r from column roi_x on, zero up to the pitch; rows from roi_h on are zero.  The source is read as ALIGNED
+// dwords that are funnel-shifted into place.  No load touches a byte outside the image [img, img + img_bytes): the
+// dword that straddles the first or the last byte of the image is put together from byte loads of the bytes the
+// segment wants, and a dword the segment wants nothing of is not loaded.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+
+namespace mpe {
+
+// one slot of a submission (device table, in slot order)
+struct GatherItem {
+  const uint8_t* img;  // device image of the stream
+  int x, y, w, h;      // ROI, inside the image
+  int slot;            // destination slot
+  int pad_;
+};
+static_assert(sizeof(GatherItem) == 32, "table entries of 32 bytes");
+
+// plain loads (on the device from the global address space: global_load instead of flat_load); the host test
+// substitutes loads that check their address against the image
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MPE_GATHER_GLOBAL __attribute__((address_space(1)))
+#else
+#define MPE_GATHER_GLOBAL
+#endif
+struct GatherLoads {
+  __host__ __device__ uint32_t ld32(uintptr_t a) const { return *reinterpret_cast<const MPE_GATHER_GLOBAL uint32_t*>(a); }
+  __host__ __device__ uint32_t ld8(uintptr_t a) const { return *reinterpret_cast<const MPE_GATHER_GLOBAL uint8_t*>(a); }
+};
+
+// bytes [16 * seg, 16 * seg + 16) of slot row r -> out[0..3] (little endian).  img_bytes: the image ends with the last
+// pixel of its last row, (rows - 1) * stride + cols.
+template <class Loads>
+__host__ __device__ inline void gather_segment(const Loads& mem, const uint8_t* img, size_t img_bytes, size_t stride, int x,
+                                               int y, int w, int h, int r, int seg, uint32_t out[4]) {
+  out[0] = out[1] = out[2] = out[3] = 0;
+  const int c0 = 16 * seg;
+  if (r >= h || c0 >= w) return;
+  const int n = w - c0 < 16 ? w - c0 : 16;  // bytes wanted
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(img), hi = lo + img_bytes;
+  const uintptr_t src = lo + (size_t)(y + r) * stride + (size_t)(x + c0), end = src + (size_t)n;
+  const unsigned sh = (unsigned)(src & 3);
+  const uintptr_t base = src - sh;  // aligned; up to 3 bytes in front of src (and of the image)
+  uint32_t d[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const uintptr_t a = base + 4 * (uintptr_t)j;
+    uint32_t v = 0;
+    if (a < end) {
+      if (a >= lo && a + 4 <= hi) {
+        v = mem.ld32(a);
+      } else {  // the dword straddles an end of the image: the wanted bytes of it, one by one
+        for (int b = 0; b < 4; ++b)
+          if (a + b >= src && a + b < end) v |= mem.ld8(a + b) << (8 * b);
+      }
+    }
+    d[j] = v;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    // (v_alignbyte_b32 on the device)
+    const uint32_t v = (uint32_t)(((((uint64_t)d[i + 1]) << 32) | d[i]) >> (8 * sh));
+    const int valid = n - 4 * i;  // bytes of this dword inside the ROI row
+    out[i] = valid >= 4 ? v : (valid <= 0 ? 0u : v & ((1u << (8 * valid)) - 1u));
+  }
+}
+
+}  // namespace mpe

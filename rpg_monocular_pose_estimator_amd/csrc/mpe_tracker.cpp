@@ -495,6 +495,7 @@ struct BatchCtx {
   // each set-up (a uniform group has one), and the set-up of every lane.  mixed (the *_mixed entries) admits lanes of
   // different set-ups on one handle; otherwise every lane must have the first one's.
   bool mixed = false;
+  bool frames_on_device = false;  // imgs are device pointers (the *_device entries): the device-frame submission
   std::vector<mpe_track_setup> setups;
   std::vector<int> lane_setup, item_setup;
 
@@ -583,8 +584,8 @@ struct BatchCtx {
       pend.push_back(i);
     }
     if (items.empty()) return 0;
-    const int rc = mpe_track_step_batch_setups_submit(h, items.data(), item_setup.data(), (int)items.size(), rows, cols,
-                                                      stride, setups.data(), (int)setups.size());
+    const int rc = (frames_on_device ? mpe_track_step_batch_setups_device_submit : mpe_track_step_batch_setups_submit)(
+        h, items.data(), item_setup.data(), (int)items.size(), rows, cols, stride, setups.data(), (int)setups.size());
     if (rc != MPE_OK) {
       pend.clear();
       return rc;
@@ -780,7 +781,8 @@ mpe_tracker::~mpe_tracker() { delete solo; }
 extern "C" {
 
 static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
-                          size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated, bool mixed) {
+                          size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated, bool mixed,
+                          bool on_device = false) {
   if (!ts || n < 0 || !imgs || !times) return MPE_ERR_ARG;
   if (n == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -788,6 +790,7 @@ static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* i
   BatchCtx c;
   int rc = c.validate(ts, n, mixed);
   if (rc != MPE_OK) return rc;
+  c.frames_on_device = on_device;
   c.begin(imgs, rows, cols, stride_bytes, times);
   if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
     c.cancel();  // (a submission may still be in flight: leave the handle usable)
@@ -826,6 +829,12 @@ int mpe_tracker_estimate_batch_mixed(mpe_tracker* const* ts, int n, const uint8_
   return estimate_batch(ts, n, imgs, rows, cols, stride_bytes, times, out, info, updated, true);
 }
 
+// the frames in device memory (host array of device pointers); set-ups may be mixed, as in the entry above
+int mpe_tracker_estimate_batch_device(mpe_tracker* const* ts, int n, const uint8_t* const* d_imgs, int rows, int cols,
+                                      size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated) {
+  return estimate_batch(ts, n, d_imgs, rows, cols, stride_bytes, times, out, info, updated, true, true);
+}
+
 // The lock-step loops of N streams over recorded sequences.  Trackers that live on DIFFERENT handles form groups
 // (one group per handle, each with the same camera / marker / parameter set inside the group); the groups are
 // pipelined against each other: while the device works on step k of one group, the host collects, advances and
@@ -833,7 +842,7 @@ int mpe_tracker_estimate_batch_mixed(mpe_tracker* const* ts, int n, const uint8_
 // (mixed: each group may mix cameras, marker sets and parameters — mpe_tracker_run_sequences_batch_mixed_threads)
 static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows, int cols,
                                size_t stride_bytes, size_t frame_stride_bytes, const double* times, mpe_result* out,
-                               int* info, int n_threads, bool mixed) {
+                               int* info, int n_threads, bool mixed, bool on_device = false) {
   if (!ts || n < 0 || !frames || !times || n_frames < 0 || n_threads < 1) return MPE_ERR_ARG;
   if (n == 0 || n_frames == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -861,6 +870,7 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
     gtimes[g].resize(members[g].size());
     const int rc = ctx[g].validate(gts[g].data(), (int)gts[g].size(), mixed);
     if (rc != MPE_OK) return rc;
+    ctx[g].frames_on_device = on_device;
   }
   // The groups gs[0..) on the calling thread, pipelined against each other: while the device works on step k of one
   // group, the host collects, advances and packs another.  Groups share nothing (own handle, own trackers, own rows
@@ -941,6 +951,15 @@ int mpe_tracker_run_sequences_batch_mixed_threads(mpe_tracker* const* ts, int n,
                                                   int* info, int n_threads) {
   return run_sequences_batch(ts, n, frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
                              n_threads, true);
+}
+
+// frames[i] = DEVICE pointer to stream i's sequence (host array of device pointers); groups as in the entry above
+int mpe_tracker_run_sequences_batch_device_threads(mpe_tracker* const* ts, int n, const uint8_t* const* d_frames,
+                                                   int n_frames, int rows, int cols, size_t stride_bytes,
+                                                   size_t frame_stride_bytes, const double* times, mpe_result* out,
+                                                   int* info, int n_threads) {
+  return run_sequences_batch(ts, n, d_frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
+                             n_threads, true, true);
 }
 
 int mpe_tracker_run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows,
