@@ -97,7 +97,8 @@ def source_fingerprint():
     import hashlib
     hsh = hashlib.sha256()
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
-                                  "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp"):
+                                  "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
+                                  "mpe_gather.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -211,20 +212,12 @@ def load_library():
     return lib
 
 
-def tracker_estimate_batch(trackers, imgs, times, mixed=False):
-    """mpe_tracker_estimate_batch: frame k of N trackers (same handle / camera / markers / parameters) in lock step,
-    one device submission per step in steady state.  imgs: list of (rows, cols) uint8 arrays; times: N floats.
-    mixed: mpe_tracker_estimate_batch_mixed (the trackers may differ in camera, markers and parameters).
-    -> (records [RESULT_DTYPE] (N), info (N,8) int32, updated (N) bool)."""
+def _estimate_batch(name, trackers, ptrs, rows, cols, stride, times):
+    """One lock-step time step through entry `name`: ptrs = the trackers' images (host or device addresses) of one
+    shape and row stride.  -> (records (N), info (N,8), updated (N) bool)."""
     lib = load_library()
-    name = "mpe_tracker_estimate_batch_mixed" if mixed else "mpe_tracker_estimate_batch"
     n = len(trackers)
-    imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
-    rows, cols = imgs[0].shape
-    stride = imgs[0].strides[0]
-    assert all(im.shape == (rows, cols) and im.strides[0] == stride for im in imgs)
     ts = (C.c_void_p * n)(*[t._t for t in trackers])
-    ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
     times = _f64(times).reshape(-1)
     rec = np.zeros(n, RESULT_DTYPE)
     info = np.zeros((n, 8), np.int32)
@@ -234,6 +227,36 @@ def tracker_estimate_batch(trackers, imgs, times, mixed=False):
     if rc < 0:
         raise MpeError("%s failed (%d): %s" % (name, rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
     return rec, info, upd.astype(bool)
+
+
+def _run_sequences_batch(name, trackers, ptrs, n, rows, cols, stride, fstride, times, threads):
+    """The lock-step loop in C through entry `name`: ptrs = the trackers' sequences (host or device addresses) of n
+    frames each, one shape, row stride and frame stride.  -> (records (N,n), info (N,n,8))."""
+    lib = load_library()
+    N = len(trackers)
+    ts = (C.c_void_p * N)(*[t._t for t in trackers])
+    times = _f64(times).reshape(-1)
+    rec = np.zeros((N, n), RESULT_DTYPE)
+    info = np.zeros((N, n, 8), np.int32)
+    rc = getattr(lib, name)(ts, N, ptrs, n, rows, cols, stride, fstride, _dp(times), rec.ctypes.data, info.ctypes.data,
+                            int(threads))
+    if rc < 0:
+        raise MpeError("%s failed (%d): %s" % (name, rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
+    return rec, info
+
+
+def tracker_estimate_batch(trackers, imgs, times, mixed=False):
+    """mpe_tracker_estimate_batch: frame k of N trackers (same handle / camera / markers / parameters) in lock step,
+    one device submission per step in steady state.  imgs: list of (rows, cols) uint8 arrays; times: N floats.
+    mixed: mpe_tracker_estimate_batch_mixed (the trackers may differ in camera, markers and parameters).
+    -> (records [RESULT_DTYPE] (N), info (N,8) int32, updated (N) bool)."""
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in imgs]
+    rows, cols = imgs[0].shape
+    stride = imgs[0].strides[0]
+    assert all(im.shape == (rows, cols) and im.strides[0] == stride for im in imgs)
+    ptrs = (C.c_void_p * len(trackers))(*[im.ctypes.data for im in imgs])
+    return _estimate_batch("mpe_tracker_estimate_batch_mixed" if mixed else "mpe_tracker_estimate_batch", trackers, ptrs,
+                           rows, cols, stride, times)
 
 
 def tracker_estimate_batch_mixed(trackers, imgs, times):
@@ -247,22 +270,13 @@ def tracker_run_sequences_batch(trackers, frames, times, threads=1, mixed=False)
     (one sequence per tracker), times: n floats; threads > 1: the handle groups on that many host threads.
     mixed: mpe_tracker_run_sequences_batch_mixed_threads (groups by handle alone, each may mix set-ups).
     -> (records (N,n), info (N,n,8))."""
-    lib = load_library()
-    name = "mpe_tracker_run_sequences_batch_mixed_threads" if mixed else "mpe_tracker_run_sequences_batch_threads"
-    N = len(trackers)
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     n, rows, cols = frames[0].shape
     assert all(f.shape == (n, rows, cols) for f in frames)
-    ts = (C.c_void_p * N)(*[t._t for t in trackers])
-    ptrs = (C.c_void_p * N)(*[f.ctypes.data for f in frames])
-    times = _f64(times).reshape(-1)
-    rec = np.zeros((N, n), RESULT_DTYPE)
-    info = np.zeros((N, n, 8), np.int32)
-    rc = getattr(lib, name)(ts, N, ptrs, n, rows, cols, frames[0].strides[1], frames[0].strides[0], _dp(times),
-                            rec.ctypes.data, info.ctypes.data, int(threads))
-    if rc < 0:
-        raise MpeError("%s failed (%d): %s" % (name, rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
-    return rec, info
+    ptrs = (C.c_void_p * len(trackers))(*[f.ctypes.data for f in frames])
+    return _run_sequences_batch("mpe_tracker_run_sequences_batch_mixed_threads" if mixed
+                                else "mpe_tracker_run_sequences_batch_threads", trackers, ptrs, n, rows, cols,
+                                frames[0].strides[1], frames[0].strides[0], times, threads)
 
 
 def tracker_run_sequences_batch_mixed(trackers, frames, times, threads=1):
@@ -294,43 +308,19 @@ def tracker_estimate_batch_device(trackers, imgs, times):
     list of (rows, cols) torch uint8 CUDA tensors, one per tracker, or one (N, rows, cols) tensor, on the device of the
     trackers' handle.  The trackers may mix set-ups.  -> (records (N), info (N,8), updated (N) bool), those of the host
     entries over the same frames."""
-    lib = load_library()
-    n = len(trackers)
-    keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0)
-    assert len(keep) == n
-    ts = (C.c_void_p * n)(*[t._t for t in trackers])
-    times = _f64(times).reshape(-1)
-    rec = np.zeros(n, RESULT_DTYPE)
-    info = np.zeros((n, 8), np.int32)
-    upd = np.zeros(n, np.int32)
-    rc = lib.mpe_tracker_estimate_batch_device(ts, n, ptrs, rows, cols, stride, _dp(times), rec.ctypes.data,
-                                               info.ctypes.data, upd.ctypes.data)
-    del keep
-    if rc < 0:
-        raise MpeError("mpe_tracker_estimate_batch_device failed (%d): %s"
-                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
-    return rec, info, upd.astype(bool)
+    keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0)  # (keep: the tensors stay alive across the call)
+    assert len(keep) == len(trackers)
+    return _estimate_batch("mpe_tracker_estimate_batch_device", trackers, ptrs, rows, cols, stride, times)
 
 
 def tracker_run_sequences_batch_device(trackers, frames, times, threads=1):
     """mpe_tracker_run_sequences_batch_device_threads: tracker_run_sequences_batch[_mixed] over sequences that are in
     device memory — frames: a list of (n, rows, cols) torch uint8 CUDA tensors, one per tracker, or one (N, n, rows, cols)
     tensor.  Each handle's trackers form one lock-step group that may mix set-ups.  -> (records (N,n), info (N,n,8))."""
-    lib = load_library()
-    N = len(trackers)
-    keep, ptrs, (n, rows, cols), (fstride, stride, _) = _device_images(frames, 1)
-    assert len(keep) == N
-    ts = (C.c_void_p * N)(*[t._t for t in trackers])
-    times = _f64(times).reshape(-1)
-    rec = np.zeros((N, n), RESULT_DTYPE)
-    info = np.zeros((N, n, 8), np.int32)
-    rc = lib.mpe_tracker_run_sequences_batch_device_threads(ts, N, ptrs, n, rows, cols, stride, fstride, _dp(times),
-                                                            rec.ctypes.data, info.ctypes.data, int(threads))
-    del keep
-    if rc < 0:
-        raise MpeError("mpe_tracker_run_sequences_batch_device_threads failed (%d): %s"
-                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
-    return rec, info
+    keep, ptrs, (n, rows, cols), (fstride, stride, _) = _device_images(frames, 1)  # (keep: alive across the call)
+    assert len(keep) == len(trackers)
+    return _run_sequences_batch("mpe_tracker_run_sequences_batch_device_threads", trackers, ptrs, n, rows, cols, stride,
+                                fstride, times, threads)
 
 
 class TrackItem(C.Structure):  # mpe_track_item

@@ -2,7 +2,8 @@
 // file; it is now mpe_schedule.cpp — parameter marshalling, workspaces, the schedules of a batch (run_pipeline) —,
 // mpe_options.cpp — handle life cycle, streams, profiling read-outs, mpe_set_option / mpe_get_option —,
 // mpe_track_abi.cpp — tracked frames and lock-step time steps — and mpe_abi.cpp — every other entry of include/mpe.h;
-// same exported symbols).  No torch, no CPU fallback: without a HIP device every entry point fails with
+// same exported symbols; mpe_track_device.hip holds the one kernel that is launched from here and is no part of
+// mpe_k1 / k2 / k3: the ROI gather of device-resident frames).  No torch, no CPU fallback: without a HIP device every entry point fails with
 // MPE_ERR_NO_DEVICE / MPE_ERR_HIP.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +32,9 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
 
 #include "mpe_internal.h"
 
+namespace mpe {
+struct GatherItem;  // (mpe_gather.h)
+}
 using namespace mpe;
 
 struct DevBuf {
@@ -281,6 +285,11 @@ int run_pipeline(mpe_handle* h, const uint8_t* d_frames, int n_frames, const Fra
                  const SolveParams* sp, mpe_detections* d_dets, uint32_t* d_hist, mpe_result* d_results,
                  uint32_t* d_corr, const StreamHint* hint = nullptr);
 int last_kernel_ms_of_call(mpe_handle* h, float ms[5]);  // (mpe_options.cpp)
+// the ROI slots of a lock-step submission gathered from images in device memory (mpe_track_device.hip; the table entry
+// is defined in mpe_gather.h): slot tab[e].slot of dst from image tab[e].img, n entries, on stream s.  (Hidden: until
+// it had a caller in another translation unit it was no exported name, and nothing outside the library calls it.)
+__attribute__((visibility("hidden"))) hipError_t launch_gather_rois(const GatherItem* tab, int n, uint8_t* dst, const FrameGeom& g, size_t stride, size_t img_bytes,
+                              hipStream_t s);
 // the text of mpe_last_error, for mpe_tracker.cpp (which sees only the C ABI and declares this itself; mpe_options.cpp)
 void set_error(mpe_handle* h, const char* what);
 }  // namespace mpe_host

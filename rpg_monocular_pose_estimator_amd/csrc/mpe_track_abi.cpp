@@ -1,8 +1,10 @@
 // mpe_track_abi.cpp — host side of libmpe_hip.so, part 3 (see mpe_host.h): one tracked frame (mpe_track_step) and the
-// lock-step time step of N camera streams (mpe_track_step_batch[_setups][_submit / _collect / _cancel]); the per-stream
-// state machine on top of them is mpe_tracker.cpp.  Every entry checks its own arguments and then makes the same
-// submission (submit_slots): a uniform batch is the submission of one set-up, a tracked frame a batch of one.
+// lock-step time step of N camera streams (mpe_track_step_batch[_setups][_device][_submit / _collect / _cancel]); the
+// per-stream state machine on top of them is mpe_tracker.cpp.  Every entry checks its own arguments and then makes the
+// same submission (submit_slots): a uniform batch is the submission of one set-up, a tracked frame a batch of one, and
+// frames in device memory differ only in where the ROI slots come from (a gather kernel instead of a host copy).
 #include "mpe_host.h"
+#include "mpe_gather.h"
 
 extern "C" {
 
@@ -52,6 +54,42 @@ void pack_roi(uint8_t* slot, const FrameGeom& g, const mpe_track_item& it, size_
       std::memset(dst, 0, (size_t)g.pitch);
     }
   }
+}
+
+// Every item's image must be a device allocation on the handle's device that holds the whole image: this check is what
+// stands between a caller's mistake and a GPU fault.  Each distinct allocation is looked up once per call (the frames
+// of N streams usually sit in one or a few).  (static, as prepare_setups below: inside extern "C" the unnamed namespace
+// alone does not keep a name out of the library's exports, and these two are no part of them)
+static int check_device_images(mpe_handle* h, const mpe_track_item* items, int n, size_t img_bytes) {
+  struct Span {
+    uintptr_t lo, hi;
+  };
+  std::vector<Span> ok;
+  for (int i = 0; i < n; ++i) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(items[i].img);
+    bool known = false;
+    for (const Span& s : ok) known |= a >= s.lo && a + img_bytes <= s.hi;
+    if (known) continue;
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, items[i].img) != hipSuccess) {
+      (void)hipGetLastError();  // (an ordinary host pointer: the runtime reports it as an error)
+      return fail(h, MPE_ERR_ARG, "img is not a device pointer (the host entries are for that)");
+    }
+    if (at.type != hipMemoryTypeDevice)
+      return fail(h, MPE_ERR_ARG, "img is not a device allocation (the host entries are for that)");
+    if (at.device != h->device) return fail(h, MPE_ERR_ARG, "img is on another device than the handle");
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<uint8_t*>(items[i].img)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(h, MPE_ERR_ARG, "img is not inside a device allocation");
+    }
+    const Span s = {reinterpret_cast<uintptr_t>(base), reinterpret_cast<uintptr_t>(base) + size};
+    if (a < s.lo || a + img_bytes > s.hi) return fail(h, MPE_ERR_ARG, "the image reaches beyond its device allocation");
+    ok.push_back(s);
+  }
+  return MPE_OK;
 }
 
 // the device workspaces of n slots of geometry g behind in_bytes of inputs
@@ -112,9 +150,16 @@ int track_range_chain(mpe_handle* h, const mpe_handle::PendingTrack::Range& r, i
 // nearest-neighbour correspondences from the stream's predicted pixels, validate, refine) runs them, and every rare
 // path (track_fused 0, set-ups of more than 8 markers, the re-run of a range that overflowed the small blob tier) is
 // the chain of kernels over a range with its own parameters.  One copy brings the N records back; _collect un-permutes
-// them.  The caller has checked the arguments and entered the handle.
+// them.  Where the pixels are is the one thing that varies: host frames are packed into the staging memory (pack_roi)
+// and travel with the header; of device frames (img_bytes each: an image ends with the last pixel of its last row) the
+// header carries a gather table instead and k_gather_rois writes the same slot bytes on the device, in front of
+// everything that reads them.  The caller has checked the arguments and entered the handle.
+enum PixelSource { kHostFrames, kDeviceFrames };
+
 int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, const FrameGeom& g,
-                 size_t stride_bytes, const TrackSetup* setups, int n_setups) {
+                 size_t stride_bytes, const TrackSetup* setups, int n_setups, PixelSource source = kHostFrames,
+                 size_t img_bytes = 0) {
+  const bool on_device = source == kDeviceFrames;
   mpe_handle::PendingTrack& pt = h->pending_track;
   pt.t_in = h->track_profile ? clk::now() : clk::time_point();
   auto setup_of = [item_setup](int i) { return item_setup ? item_setup[i] : 0; };
@@ -141,7 +186,8 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     const int r = range_of[(size_t)setup_of(i)];
     pt.perm[(size_t)(pt.ranges[(size_t)r].begin + fill[(size_t)r]++)] = i;
   }
-  // [predictions | windows | set-up table | slot -> set-up | ROI slots] in slot order: one H2D copy.  The table only for
+  // [predictions | windows | set-up table | slot -> set-up | gather table (device frames) | ROI slots] in slot order; one
+  // H2D copy carries what the host has of it: all of it, or the header in front of the slots.  The set-up table only for
   // a launch of two or more set-ups: one set-up goes as kernel arguments (the table instantiation is 5.6 % slower)
   const bool table = fused_setups >= 2;
   const size_t slot = (size_t)g.rows * g.pitch;
@@ -149,14 +195,17 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   const size_t win_bytes = ((size_t)n * 4 * sizeof(int) + 15) & ~(size_t)15;
   const size_t tab_bytes = table ? (pt.ranges.size() * sizeof(TrackSetup) + 255) & ~(size_t)255 : 0;
   const size_t idx_bytes = table ? ((size_t)n * sizeof(int) + 15) & ~(size_t)15 : 0;
-  const size_t head_bytes = pred_bytes + win_bytes + tab_bytes + idx_bytes;
+  const size_t gat_off = pred_bytes + win_bytes + tab_bytes + idx_bytes;
+  const size_t head_bytes = gat_off + (on_device ? (size_t)n * sizeof(GatherItem) : 0);  // (a multiple of 16: the slots' alignment)
   const size_t in_bytes = head_bytes + (size_t)n * slot;
+  const size_t staged_bytes = on_device ? head_bytes : in_bytes;
   const size_t rec_bytes = TrackRecords::bytes(n);
-  int rc = grow_mailbox(h, in_bytes + rec_bytes + 256);
+  int rc = grow_mailbox(h, staged_bytes + rec_bytes + 512);
   if (rc != MPE_OK) return rc;
   uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
   double* pred = reinterpret_cast<double*>(mb);
   int* wins = reinterpret_cast<int*>(mb + pred_bytes);
+  GatherItem* gat = reinterpret_cast<GatherItem*>(mb + gat_off);
   if (table) {
     TrackSetup* tab = reinterpret_cast<TrackSetup*>(mb + pred_bytes + win_bytes);
     int* slot_setup = reinterpret_cast<int*>(mb + pred_bytes + win_bytes + tab_bytes);
@@ -177,9 +226,12 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     wins[4 * k + 1] = it.roi_w;
     wins[4 * k + 2] = it.roi_x;
     wins[4 * k + 3] = it.roi_y;
-    pack_roi(mb + head_bytes + (size_t)k * slot, g, it, stride_bytes);
+    if (on_device)
+      gat[k] = GatherItem{it.img, it.roi_x, it.roi_y, it.roi_w, it.roi_h, k, 0};
+    else
+      pack_roi(mb + head_bytes + (size_t)k * slot, g, it, stride_bytes);
   }
-  uint8_t* host_rec = mb + ((in_bytes + 255) & ~(size_t)255);
+  uint8_t* host_rec = mb + ((staged_bytes + 255) & ~(size_t)255);
   if ((rc = reserve_track(h, g, n, in_bytes)) != MPE_OK) return rc;
   uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
   h->have_ms = false;
@@ -187,13 +239,16 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   // (Zero-copy I/O — the kernels reading the pinned mailbox over PCIe, a copy kernel writing the record back — was
   //  built and measured in round 3: the image scan then waits for PCIe reads (4 -> 46 us for 64 streams) and the step
   //  is no faster, 0.135 vs 0.136 ms for one stream.  The two copy commands stay.)
-  HIP_TRY(h, hipMemcpyAsync(d_in, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d_in, mb, staged_bytes, hipMemcpyHostToDevice, h->stream));
   pt.g = g;
   pt.slot_bytes = slot;
   pt.rec_bytes = rec_bytes;
   pt.d_pred = reinterpret_cast<const double*>(d_in);
   pt.d_wins = d_in + pred_bytes;
   pt.d_pix = d_in + head_bytes;
+  if (on_device)
+    HIP_TRY(h, launch_gather_rois(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g, stride_bytes,
+                                  img_bytes, h->stream));
   ++h->track_batch_submits;
   // round 6: the fused ranges as ONE launch, a block per stream (k_track_frame), the records stored to the pinned
   // staging memory by the kernel (track_fused 2) — scan, small blob tier, tail and copy-out were five commands, and
@@ -224,6 +279,42 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   h->pending_track_rec = host_rec;
   return MPE_OK;
 }
+
+// What the _setups entries (host and device frames) check behind their own argument condition, every usage error before
+// any device work: no submission in flight, the set-ups, every item's set-up index and ROI (item_setup null: set-up 0);
+// then the slot geometry g and the prepared parameters of the set-ups that have streams.  n == 0: MPE_OK with nothing
+// prepared — there is nothing to submit.
+static int prepare_setups(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows, int cols,
+                          const mpe_track_setup* setups, int n_setups, FrameGeom& g, std::vector<TrackSetup>& prep) {
+  if (h->pending_track_n) return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+  for (int s = 0; s < n_setups; ++s) {
+    const mpe_track_setup& su = setups[s];
+    if (!su.p || !su.K || !su.markers_xyz || su.nD < 0 || (su.nD > 0 && !su.D))
+      return fail(h, MPE_ERR_ARG, "bad set-up");
+    if (su.n_markers < 0 || su.n_markers > MPE_MAX_MARKERS) return fail(h, MPE_ERR_ARG, "set-up with n_markers > MPE_MAX_MARKERS");
+  }
+  int rmax = 0, wmax = 0;
+  std::vector<char> used((size_t)n_setups, 0);
+  for (int i = 0; i < n; ++i) {
+    const int s = item_setup ? item_setup[i] : 0;
+    if (s < 0 || s >= n_setups) return fail(h, MPE_ERR_ARG, "set-up index out of range");
+    if (!items[i].img || !roi_inside(items[i], rows, cols)) return fail(h, MPE_ERR_ARG, "ROI outside the image");
+    used[(size_t)s] = 1;
+    rmax = std::max(rmax, items[i].roi_h);
+    wmax = std::max(wmax, items[i].roi_w);
+  }
+  if (n == 0) return MPE_OK;
+  if (make_geom(h, rmax, wmax, g)) return fail(h, MPE_ERR_UNSUPPORTED, "frame size unsupported");
+  prep = std::vector<TrackSetup>((size_t)n_setups);
+  for (int s = 0; s < n_setups; ++s) {  // (the set-ups that have streams)
+    const mpe_track_setup& su = setups[s];
+    if (!used[(size_t)s]) continue;
+    if (make_detect_params(su.p, su.K, su.D, su.nD, 0, 0, prep[(size_t)s].dp)) return fail(h, MPE_ERR_ARG, "gaussian_sigma must be in (0, 6]");
+    if (make_solve_params(h, su.p, su.markers_xyz, su.n_markers, su.K, prep[(size_t)s].sp)) return fail(h, MPE_ERR_ARG, "bad set-up");
+    prep[(size_t)s].nn_tol = su.p->nearest_neighbour_pixel_tolerance;
+  }
+  return MPE_OK;
+}
 }  // namespace
 
 int mpe_track_step_batch_submit(mpe_handle* h, const mpe_track_item* items, int n, int rows, int cols,
@@ -252,35 +343,39 @@ int mpe_track_step_batch_setups_submit(mpe_handle* h, const mpe_track_item* item
                                        int cols, size_t stride_bytes, const mpe_track_setup* setups, int n_setups) {
   // every usage error before any device work
   if (!h || !items || !item_setup || n < 0 || !setups || n_setups < 1) return fail(h, MPE_ERR_ARG, "bad argument");
-  if (h->pending_track_n) return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
-  for (int s = 0; s < n_setups; ++s) {
-    const mpe_track_setup& su = setups[s];
-    if (!su.p || !su.K || !su.markers_xyz || su.nD < 0 || (su.nD > 0 && !su.D))
-      return fail(h, MPE_ERR_ARG, "bad set-up");
-    if (su.n_markers < 0 || su.n_markers > MPE_MAX_MARKERS) return fail(h, MPE_ERR_ARG, "set-up with n_markers > MPE_MAX_MARKERS");
-  }
-  int rmax = 0, wmax = 0;
-  std::vector<char> used((size_t)n_setups, 0);
-  for (int i = 0; i < n; ++i) {
-    if (item_setup[i] < 0 || item_setup[i] >= n_setups) return fail(h, MPE_ERR_ARG, "set-up index out of range");
-    if (!items[i].img || !roi_inside(items[i], rows, cols)) return fail(h, MPE_ERR_ARG, "ROI outside the image");
-    used[(size_t)item_setup[i]] = 1;
-    rmax = std::max(rmax, items[i].roi_h);
-    wmax = std::max(wmax, items[i].roi_w);
-  }
-  if (n == 0) return MPE_OK;
   FrameGeom g;
-  if (make_geom(h, rmax, wmax, g)) return fail(h, MPE_ERR_UNSUPPORTED, "frame size unsupported");
-  std::vector<TrackSetup> prep((size_t)n_setups);
-  for (int s = 0; s < n_setups; ++s) {  // (the set-ups that have streams)
-    const mpe_track_setup& su = setups[s];
-    if (!used[(size_t)s]) continue;
-    if (make_detect_params(su.p, su.K, su.D, su.nD, 0, 0, prep[(size_t)s].dp)) return fail(h, MPE_ERR_ARG, "gaussian_sigma must be in (0, 6]");
-    if (make_solve_params(h, su.p, su.markers_xyz, su.n_markers, su.K, prep[(size_t)s].sp)) return fail(h, MPE_ERR_ARG, "bad set-up");
-    prep[(size_t)s].nn_tol = su.p->nearest_neighbour_pixel_tolerance;
-  }
+  std::vector<TrackSetup> prep;
+  const int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
+  if (rc != MPE_OK || n == 0) return rc;
   ENTER(h);
   return submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups);
+}
+
+int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                                              int rows, int cols, size_t stride_bytes, const mpe_track_setup* setups,
+                                              int n_setups) {
+  // every usage error before any device work, with the codes and messages of mpe_track_step_batch_setups_submit
+  if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || rows < 1 || cols < 1 ||
+      stride_bytes < (size_t)cols)
+    return fail(h, MPE_ERR_ARG, "bad argument");
+  FrameGeom g;
+  std::vector<TrackSetup> prep;
+  int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
+  if (rc != MPE_OK || n == 0) return rc;
+  ENTER(h);
+  const size_t img_bytes = (size_t)(rows - 1) * stride_bytes + (size_t)cols;
+  if ((rc = check_device_images(h, items, n, img_bytes)) != MPE_OK) return rc;
+  return submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups, kDeviceFrames, img_bytes);
+}
+
+int mpe_track_step_batch_setups_device(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows,
+                                       int cols, size_t stride_bytes, const mpe_track_setup* setups, int n_setups,
+                                       mpe_detections* dets_out, uint32_t* corr_out, mpe_result* out) {
+  if (!dets_out || !corr_out || !out) return fail(h, MPE_ERR_ARG, "bad argument");
+  const int rc = mpe_track_step_batch_setups_device_submit(h, items, item_setup, n, rows, cols, stride_bytes, setups, n_setups);
+  if (rc != MPE_OK) return rc;
+  if (n == 0) return MPE_OK;  // (nothing was submitted)
+  return mpe_track_step_batch_collect(h, dets_out, corr_out, out);
 }
 
 int mpe_track_step_batch_setups(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows, int cols,
