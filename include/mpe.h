@@ -388,6 +388,21 @@ int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_ite
 int mpe_solve_bruteforce_batch(mpe_handle* h, const double* det_xy, const int* n_det, int n,
                                const double* markers_xyz, int n_markers, const double K[9], const mpe_params* p,
                                mpe_result* out, uint32_t* hist, uint32_t* corr);
+/* mpe_solve_bruteforce_batch for detection sets that differ in camera, marker set and parameters:
+ * item i runs with setups[item_setup[i]] (mpe_track_setup; its D / nD are not read here).
+ * det_xy n x MPE_MAX_DETECTIONS x 2, n_det[i] valid rows; hist (optional) n x MPE_MAX_DETECTIONS x
+ * MPE_MAX_MARKERS, corr (optional) n x 2*MPE_MAX_MARKERS; records in the caller's item order.
+ * Every item's record, correspondence rows and histogram are byte-identical to what mpe_solve_bruteforce_batch returns
+ * for the items of its set-up alone, under the handle's current options.  Items of two or more set-ups are ONE device
+ * submission — one input copy, one memset, one voting launch, one tail launch, one copy back, whatever n_setups is
+ * (get "bruteforce_submits" counts the submissions of the brute-force solve entries); items of one set-up, and every
+ * call with vote_arith 2, go through mpe_solve_bruteforce_batch, one call per set-up that has items.
+ * n == 0: MPE_OK.  item_setup == NULL only with n_setups == 1.  A set-up that no item names is legal.  MPE_ERR_ARG
+ * before any device work: null pointers, a set-up index out of range, n_markers outside 1 .. MPE_MAX_MARKERS, n_det[i]
+ * outside 0 .. MPE_MAX_DETECTIONS, a lock-step or streaming submission of the handle not collected yet. */
+int mpe_solve_bruteforce_batch_setups(mpe_handle* h, const double* det_xy, const int* n_det, const int* item_setup, int n,
+                                      const mpe_track_setup* setups, int n_setups, mpe_result* out, uint32_t* hist,
+                                      uint32_t* corr);
 
 /* ---- stateful estimator: the whole PoseEstimator::estimateBodyPose state machine, i.e. the
  * uninitialised branch AND the tracking path (pose_estimator.cpp:62-147): pose prediction by the
@@ -443,7 +458,8 @@ int mpe_tracker_run_sequences_batch_threads(mpe_tracker* const* trackers, int n,
  * camera: pose_estimator.h:63,82-83, monocular_pose_estimator.cpp:103-120).  The trackers must be distinct and on the
  * SAME handle (else MPE_ERR_ARG before any device work).  The ROI / whole-image detections of a time step go through
  * mpe_track_step_batch_setups — in steady state ONE device submission and one launch for all N streams —, the
- * re-initialisations through one mpe_solve_bruteforce_batch per set-up that has any.  Results are identical to calling
+ * re-initialisations of a step through ONE mpe_solve_bruteforce_batch_setups over the streams of every set-up that has
+ * any (mpe_solve_bruteforce_batch when only one set-up has).  Results are identical to calling
  * mpe_tracker_estimate per stream, and to mpe_tracker_estimate_batch over each set-up's trackers alone. */
 int mpe_tracker_estimate_batch_mixed(mpe_tracker* const* trackers, int n, const uint8_t* const* imgs, int rows, int cols,
                                      size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated);
@@ -459,7 +475,7 @@ int mpe_tracker_run_sequences_batch_mixed_threads(mpe_tracker* const* trackers, 
  * d_imgs / d_frames are HOST arrays of device pointers (d_imgs[i] stream i's frame, d_frames[i] stream i's sequence),
  * on the device of the trackers' handle.  The ROI and whole-image detections go through
  * mpe_track_step_batch_setups_device_submit instead of the host-frame submission — no frame and no ROI crosses PCIe —,
- * the re-initialisations through mpe_solve_bruteforce_batch on detections that are on the host anyway.  The trackers
+ * the re-initialisations through mpe_solve_bruteforce_batch[_setups] on detections that are on the host anyway.  The trackers
  * may mix set-ups (the _mixed rules: distinct trackers, one handle per group).  Records and info are byte-identical to
  * those of the host-frame entries over the same frames.  Ordering as for mpe_track_step_batch_setups_device: the
  * frames are final in the order of the handle's stream at the call and unmodified until it returns. */
@@ -590,6 +606,9 @@ int mpe_set_option(mpe_handle* h, const char* name, int value);
  *   that ran through the chain of kernels instead of the one fused launch (track_fused 0, more than 8 markers), and
  *   set-ups repeated through that chain by _collect because a slot overflowed the small blob tier; since the handle was
  *   made.
+ * get "bruteforce_submits": device submissions of the brute-force solve entries since the handle was made
+ *   (mpe_solve_bruteforce, mpe_initialise, mpe_solve_bruteforce_batch: one per call; mpe_solve_bruteforce_batch_setups:
+ *   one for a call that goes out fused, else one per set-up that has items; the trackers' re-initialisations included).
  * get "overflow_frames", "overflow_general", "overflow_why_1" .. "overflow_why_6": frames of the last pipelined batch
  *   that the first blob tier handed on, in all / to the general tier / by the capacity exceeded (bright segments,
  *   bands, islands, pixel pool, bitmap pool, blobs kept); synchronises.

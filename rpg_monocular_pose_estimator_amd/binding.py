@@ -98,7 +98,7 @@ def source_fingerprint():
     hsh = hashlib.sha256()
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
-                                  "mpe_gather.h"):
+                                  "mpe_gather.h", "mpe_brute_blocks.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -149,6 +149,11 @@ def load_library():
                                   C.POINTER(C.c_int)]
     lib.mpe_solve_bruteforce.argtypes = [C.c_void_p, dp, C.c_int, dp, C.c_int, dp, C.POINTER(MpeParams),
                                          C.POINTER(MpeResult), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    ip, up = C.POINTER(C.c_int), C.POINTER(C.c_uint32)
+    lib.mpe_solve_bruteforce_batch.argtypes = [C.c_void_p, dp, ip, C.c_int, dp, C.c_int, dp, C.POINTER(MpeParams),
+                                               C.c_void_p, up, up]
+    lib.mpe_solve_bruteforce_batch_setups.argtypes = [C.c_void_p, dp, ip, ip, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                      up, up]
     lib.mpe_estimate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
                                        C.c_int, dp, C.c_int, dp, dp, C.c_int, C.POINTER(MpeParams), C.c_void_p]
     lib.mpe_estimate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, dp,
@@ -603,6 +608,60 @@ class Handle:
         return dict(status=res.status, T=np.array(res.T).reshape(4, 4), cov=np.array(res.cov).reshape(6, 6),
                     n_det=res.n_det, n_corr=res.n_corr, gn_iterations=res.gn_iterations,
                     hist=hist[:len(det)].copy(), corr=corr[:res.n_corr].copy())
+
+    # ---- the same for N detection sets in one call ----------------------------------------------
+    @staticmethod
+    def _pack_dets(dets):
+        n = len(dets)
+        buf = np.zeros((n, MAX_DETECTIONS, 2))
+        nd = np.zeros(n, np.int32)
+        for i, d in enumerate(dets):
+            d = _f64(d).reshape(-1, 2)
+            nd[i] = len(d)
+            buf[i, :len(d)] = d
+        return buf, nd
+
+    def solve_bruteforce_batch(self, dets, markers, K, params):
+        """mpe_solve_bruteforce_batch: dets a list of (n_i, 2) arrays, one marker set, camera and parameter set.
+        -> (records [RESULT_DTYPE] (N), histograms (N, MAX_DETECTIONS, MAX_MARKERS) uint32, correspondences
+        (N, MAX_MARKERS, 2) uint32)."""
+        markers, K = _f64(markers).reshape(-1, 3), _f64(K).reshape(9)
+        buf, nd = self._pack_dets(dets)
+        n = len(nd)
+        rec = np.zeros(n, RESULT_DTYPE)
+        hist = np.zeros((n, MAX_DETECTIONS, MAX_MARKERS), np.uint32)
+        corr = np.zeros((n, MAX_MARKERS, 2), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        rc = self._lib.mpe_solve_bruteforce_batch(self._h, _dp(buf), nd.ctypes.data_as(C.POINTER(C.c_int)), n, _dp(markers),
+                                                  len(markers), _dp(K), C.byref(params), C.c_void_p(rec.ctypes.data),
+                                                  hist.ctypes.data_as(up), corr.ctypes.data_as(up))
+        self._check(rc, "mpe_solve_bruteforce_batch")
+        return rec, hist, corr
+
+    def solve_bruteforce_batch_setups(self, dets, setups, item_setup):
+        """mpe_solve_bruteforce_batch_setups: dets a list of (n_i, 2) arrays; setups a list of (markers, K, D, params)
+        as for track_step_batch (D is not read); item_setup the set-up of every item, or None with one set-up.
+        -> (records, histograms, correspondences) as solve_bruteforce_batch, in item order."""
+        keep = []
+        su = (TrackSetup * len(setups))()
+        for s, (markers, K, D, params) in enumerate(setups):
+            markers, K, D = _f64(markers).reshape(-1, 3), _f64(K).reshape(9), _f64(D).reshape(-1)
+            keep += [markers, K, D, params]
+            su[s] = TrackSetup(C.addressof(params), K.ctypes.data, D.ctypes.data if len(D) else None, len(D),
+                               markers.ctypes.data, len(markers))
+        buf, nd = self._pack_dets(dets)
+        n = len(nd)
+        idx = None if item_setup is None else (C.c_int * n)(*[int(v) for v in item_setup])
+        rec = np.zeros(n, RESULT_DTYPE)
+        hist = np.zeros((n, MAX_DETECTIONS, MAX_MARKERS), np.uint32)
+        corr = np.zeros((n, MAX_MARKERS, 2), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        rc = self._lib.mpe_solve_bruteforce_batch_setups(self._h, _dp(buf), nd.ctypes.data_as(C.POINTER(C.c_int)), idx, n,
+                                                         su, len(setups), C.c_void_p(rec.ctypes.data),
+                                                         hist.ctypes.data_as(up), corr.ctypes.data_as(up))
+        self._check(rc, "mpe_solve_bruteforce_batch_setups")
+        del keep
+        return rec, hist, corr
 
     # ---- setCorrespondences + checkCorrespondences + optimiseAndUpdatePose ----------------------
     def check_and_refine(self, det, markers, K, params, corr):

@@ -193,6 +193,7 @@ int solve_bruteforce_impl(mpe_handle* h, const double* det_xy, const int* n_det,
   HIP_TRY(h, h->results.reserve((size_t)n * sizeof(mpe_result)));
   HIP_TRY(h, h->corr.reserve(corr_bytes));
   HIP_TRY(h, h->mid.reserve(k3_mid_bytes(n)));
+  ++h->bruteforce_submits;
   HIP_TRY(h, hipMemcpyAsync(h->dets.p, hd.data(), (size_t)n * sizeof(mpe_detections), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->hist.p, 0, hist_bytes, h->stream));
   { const int rc = prep_marker_table(h, sp); if (rc) return rc; }
@@ -577,6 +578,172 @@ int mpe_solve_bruteforce_batch(mpe_handle* h, const double* det_xy, const int* n
   if (!h || !det_xy || !n_det || n < 0 || !markers_xyz || !K || !p || !out) return fail(h, MPE_ERR_ARG, "bad argument");
   if (n == 0) return MPE_OK;
   return solve_bruteforce_impl(h, det_xy, n_det, n, markers_xyz, n_markers, K, p, out, hist, corr, 0);
+}
+
+namespace {
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// blocks per item of the fused voting launch at most: four 256-thread blocks per compute unit is what the strict loop
+// nest's registers let a CU hold, so one wide item fills the chip once
+int brute_block_cap() { return 4 * std::max(1, device_cu_count()); }
+// ... and a call whose table would exceed this many blocks (hundreds of wide items) goes per set-up instead
+constexpr size_t kBruteMaxBlocks = (size_t)1 << 18;
+
+// The items idx[0 .. m) of one set-up through solve_bruteforce_impl, gathered and scattered (idx the identity over all
+// n items: the caller's arrays as they are).
+int solve_bruteforce_gathered(mpe_handle* h, const double* det_xy, const int* n_det, const std::vector<int>& idx, int n,
+                              const mpe_track_setup& su, mpe_result* out, uint32_t* hist, uint32_t* corr) {
+  const int m = (int)idx.size();
+  bool identity = m == n;
+  for (int k = 0; identity && k < m; ++k) identity = idx[(size_t)k] == k;
+  if (identity)
+    return solve_bruteforce_impl(h, det_xy, n_det, n, su.markers_xyz, su.n_markers, su.K, su.p, out, hist, corr, 0);
+  const size_t xy = (size_t)2 * MPE_MAX_DETECTIONS, hw = MPE_HIST_WORDS, cw = (size_t)2 * MPE_MAX_MARKERS;
+  std::vector<double> g_xy((size_t)m * xy);
+  std::vector<int> g_nd((size_t)m);
+  std::vector<mpe_result> g_out((size_t)m);
+  std::vector<uint32_t> g_hist(hist ? (size_t)m * hw : 0), g_corr(corr ? (size_t)m * cw : 0);
+  for (int k = 0; k < m; ++k) {
+    const size_t i = (size_t)idx[(size_t)k];
+    g_nd[(size_t)k] = n_det[i];
+    std::memcpy(&g_xy[(size_t)k * xy], det_xy + i * xy, xy * sizeof(double));
+  }
+  const int rc = solve_bruteforce_impl(h, g_xy.data(), g_nd.data(), m, su.markers_xyz, su.n_markers, su.K, su.p,
+                                       g_out.data(), hist ? g_hist.data() : nullptr, corr ? g_corr.data() : nullptr, 0);
+  if (rc != MPE_OK) return rc;
+  for (int k = 0; k < m; ++k) {
+    const size_t i = (size_t)idx[(size_t)k];
+    out[i] = g_out[(size_t)k];
+    if (hist) std::memcpy(hist + i * hw, &g_hist[(size_t)k * hw], hw * sizeof(uint32_t));
+    if (corr) std::memcpy(corr + i * cw, &g_corr[(size_t)k * cw], cw * sizeof(uint32_t));
+  }
+  return MPE_OK;
+}
+
+// Items of two or more set-ups as ONE submission: one input copy — [detection records | SolveParams table | item ->
+// set-up | block table] from the pinned staging memory —, one memset of the histograms, k2_vote_setups, k3_tail_setups,
+// one copy of [records | correspondences | histograms] back, one synchronise.  sps[s] is prepared for every set-up that
+// has items (make_solve_params, as solve_bruteforce_impl prepares its one); max_markers the largest of them.
+int solve_bruteforce_fused(mpe_handle* h, const double* det_xy, const int* n_det, const int* item_setup, int n,
+                           const std::vector<SolveParams>& sps, int max_markers, const std::vector<BruteBlock>& blocks,
+                           mpe_result* out, uint32_t* hist, uint32_t* corr) {
+  ENTER(h);
+  const size_t tab_off = up256((size_t)n * sizeof(mpe_detections));
+  const size_t idx_off = up256(tab_off + sps.size() * sizeof(SolveParams));
+  const size_t blk_off = up256(idx_off + (size_t)n * sizeof(int));
+  const size_t head_bytes = blk_off + blocks.size() * sizeof(BruteBlock);
+  const size_t res_bytes = (size_t)n * sizeof(mpe_result), corr_bytes = (size_t)n * 2 * MPE_MAX_MARKERS * sizeof(uint32_t);
+  const size_t hist_off = up256(res_bytes + corr_bytes), hist_bytes = (size_t)n * MPE_HIST_STRIDE * sizeof(uint32_t);
+  const size_t back_bytes = hist ? hist_off + hist_bytes : res_bytes + corr_bytes;
+  const size_t back_off = up256(head_bytes);
+  { const int rc = grow_mailbox(h, back_off + back_bytes); if (rc != MPE_OK) return rc; }
+  uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
+  mpe_detections* hd = reinterpret_cast<mpe_detections*>(mb);
+  std::memset(mb, 0, blk_off);
+  for (int f = 0; f < n; ++f) {
+    hd[f].n = n_det[f];
+    std::memcpy(hd[f].undist_xy, det_xy + (size_t)f * 2 * MPE_MAX_DETECTIONS, sizeof(double) * 2 * n_det[f]);
+  }
+  std::memcpy(mb + tab_off, sps.data(), sps.size() * sizeof(SolveParams));
+  std::memcpy(mb + idx_off, item_setup, (size_t)n * sizeof(int));
+  if (!blocks.empty()) std::memcpy(mb + blk_off, blocks.data(), blocks.size() * sizeof(BruteBlock));
+  HIP_TRY(h, h->frames.reserve(head_bytes));
+  HIP_TRY(h, h->results.reserve(hist_off + hist_bytes));
+  HIP_TRY(h, h->mid.reserve(k3_mid_bytes(n)));
+  uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
+  uint8_t* d_back = static_cast<uint8_t*>(h->results.p);
+  const mpe_detections* d_dets = reinterpret_cast<const mpe_detections*>(d_in);
+  const SolveParams* d_sps = reinterpret_cast<const SolveParams*>(d_in + tab_off);
+  const int* d_idx = reinterpret_cast<const int*>(d_in + idx_off);
+  mpe_result* d_res = reinterpret_cast<mpe_result*>(d_back);
+  uint32_t* d_corr = reinterpret_cast<uint32_t*>(d_back + res_bytes);
+  uint32_t* d_hist = reinterpret_cast<uint32_t*>(d_back + hist_off);
+  ++h->bruteforce_submits;
+  HIP_TRY(h, hipMemcpyAsync(d_in, mb, head_bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemsetAsync(d_hist, 0, hist_bytes, h->stream));
+  HIP_TRY(h, launch_k2_vote_setups(d_dets, d_sps, d_idx, reinterpret_cast<const BruteBlock*>(d_in + blk_off),
+                                   (int)blocks.size(), max_markers, h->vote_arith, d_hist, h->stream));
+  HIP_TRY(h, launch_k3_tail_setups(d_dets, d_hist, n, d_sps, d_idx, max_markers, d_res, d_corr, h->mid.p, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(mb + back_off, d_back, back_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  std::memcpy(out, mb + back_off, res_bytes);
+  if (corr) std::memcpy(corr, mb + back_off + res_bytes, corr_bytes);
+  if (hist)  // (device rows are MPE_HIST_STRIDE words apart, the caller's MPE_HIST_WORDS)
+    for (int f = 0; f < n; ++f)
+      std::memcpy(hist + (size_t)f * MPE_HIST_WORDS, mb + back_off + hist_off + (size_t)f * MPE_HIST_STRIDE * sizeof(uint32_t),
+                  MPE_HIST_WORDS * sizeof(uint32_t));
+  return MPE_OK;
+}
+}  // namespace
+
+// mpe_solve_bruteforce_batch for detection sets that differ in camera, marker set and parameters: item i runs with
+// setups[item_setup[i]].  Every item's record, correspondence rows and histogram are those mpe_solve_bruteforce_batch
+// returns for the items of its set-up alone, byte for byte: the strict voting arithmetic and the fast one with its
+// strict re-evaluation give identical histograms (vote_arith 0 and 1, 4 and 3), and the tail is the same code.  Items of
+// two or more set-ups go out as ONE submission (solve_bruteforce_fused); one set-up with items, vote_arith 2 (the fast
+// arithmetic alone: the strict kernel cannot reproduce it) and calls beyond the block table's bound go through
+// solve_bruteforce_impl, one call per set-up that has items.
+int mpe_solve_bruteforce_batch_setups(mpe_handle* h, const double* det_xy, const int* n_det, const int* item_setup, int n,
+                                      const mpe_track_setup* setups, int n_setups, mpe_result* out, uint32_t* hist,
+                                      uint32_t* corr) {
+  // every usage error before any device work
+  if (!h || !det_xy || !n_det || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || !out)
+    return fail(h, MPE_ERR_ARG, "bad argument");
+  for (int s = 0; s < n_setups; ++s) {
+    const mpe_track_setup& su = setups[s];
+    if (!su.p || !su.K || !su.markers_xyz) return fail(h, MPE_ERR_ARG, "bad set-up");
+    if (su.n_markers < 1 || su.n_markers > MPE_MAX_MARKERS)
+      return fail(h, MPE_ERR_ARG, "set-up with n_markers outside 1 .. MPE_MAX_MARKERS");
+  }
+  std::vector<int> count((size_t)n_setups, 0);
+  for (int i = 0; i < n; ++i) {
+    const int s = item_setup ? item_setup[i] : 0;
+    if (s < 0 || s >= n_setups) return fail(h, MPE_ERR_ARG, "set-up index out of range");
+    if (n_det[i] < 0 || n_det[i] > MPE_MAX_DETECTIONS) return fail(h, MPE_ERR_ARG, "n_det out of range");
+    ++count[(size_t)s];
+  }
+  if (n == 0) return MPE_OK;  // (nothing to do: the handle is not looked at)
+  if (h->pending_track_n || h->submit_seq != h->collect_seq)
+    return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+  int used = 0, max_markers = 0;
+  for (int s = 0; s < n_setups; ++s)
+    if (count[(size_t)s]) {
+      ++used;
+      max_markers = std::max(max_markers, setups[s].n_markers);
+    }
+  std::vector<BruteBlock> blocks;
+  bool fused = used >= 2 && h->vote_arith != 2;
+  if (fused) {
+    HIP_TRY(h, hipSetDevice(h->device));  // (device_cu_count: of the handle's device)
+    std::vector<int> nm((size_t)n);
+    size_t total = 0;
+    const int cap = brute_block_cap();
+    for (int i = 0; i < n; ++i) {
+      nm[(size_t)i] = setups[item_setup[i]].n_markers;
+      total += (size_t)brute_parts(brute_hypotheses(n_det[i], nm[(size_t)i]), cap);
+    }
+    fused = total <= kBruteMaxBlocks;
+    if (fused) brute_block_table(n_det, nm.data(), n, cap, blocks);
+  }
+  if (fused) {
+    std::vector<SolveParams> sps((size_t)n_setups);
+    for (int s = 0; s < n_setups; ++s) {  // (the set-ups that have items; the others stay zeroed and are not read)
+      const mpe_track_setup& su = setups[s];
+      if (!count[(size_t)s]) std::memset(&sps[(size_t)s], 0, sizeof(SolveParams));
+      else if (make_solve_params(h, su.p, su.markers_xyz, su.n_markers, su.K, sps[(size_t)s])) return fail(h, MPE_ERR_ARG, "bad set-up");
+    }
+    return solve_bruteforce_fused(h, det_xy, n_det, item_setup, n, sps, max_markers, blocks, out, hist, corr);
+  }
+  std::vector<int> idx;
+  for (int s = 0; s < n_setups; ++s) {
+    if (!count[(size_t)s]) continue;
+    idx.clear();
+    for (int i = 0; i < n; ++i)
+      if ((item_setup ? item_setup[i] : 0) == s) idx.push_back(i);
+    const int rc = solve_bruteforce_gathered(h, det_xy, n_det, idx, n, setups[s], out, hist, corr);
+    if (rc != MPE_OK) return rc;
+  }
+  return MPE_OK;
 }
 
 // ---- one host process, several GPUs -----------------------------------------------------------

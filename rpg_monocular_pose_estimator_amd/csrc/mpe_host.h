@@ -111,6 +111,9 @@ struct mpe_handle {
   // set-ups of a submission that ran through the chain of kernels instead of the one launch (k_track_frame); set-ups
   // of a submission repeated through that chain in _collect (a slot overflowed the small blob tier)
   long long track_batch_submits = 0, track_batch_chains = 0, track_batch_reruns = 0;
+  // get "bruteforce_submits": device submissions of the brute-force solve entries (mpe_solve_bruteforce[_batch],
+  // mpe_initialise: one each; mpe_solve_bruteforce_batch_setups: one for a fused call, one per set-up with items otherwise)
+  long long bruteforce_submits = 0;
   int pending_track_n = 0;            // a batch submission without its _collect yet: streams in flight
   uint8_t* pending_track_rec = nullptr;
   // How many detections the frames of a pipelined call are expected to carry: picks the voting-kernel variant (from 9
@@ -252,6 +255,9 @@ int fail(mpe_handle* h, int code, const char* what, hipError_t e = hipSuccess);
 // Every entry point that re-uses the handle's device buffers on its stream: select the device and, if a streaming
 // submission still has validate / refine kernels on the internal tail stream, make the handle's stream wait for them
 int enter(mpe_handle* h);
+// the pinned staging memory h->mailbox (inputs out, records back) holds at least `need` bytes; what it held is lost when
+// it grows.  One user at a time: the tracked submissions between _submit and _collect, or one blocking call
+int grow_mailbox(mpe_handle* h, size_t need);
 unsigned num_combinations_u32(unsigned n, unsigned k);
 int make_detect_params(const mpe_params* p, const double K[9], const double* D, int nD, int roi_x, int roi_y,
                        DetectParams& dp);

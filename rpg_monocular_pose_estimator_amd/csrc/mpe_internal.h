@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/mpe.h"
+#include "mpe_brute_blocks.h"
 
 namespace mpe {
 
@@ -168,6 +169,17 @@ struct TrackSetup {
 };
 hipError_t launch_track_frames_setups(const TrackFramesArgs& t, int n_frames, const FrameGeom& g, const TrackSetup* setups,
                                       const int* slot_setup, int max_markers, hipStream_t s);
+// Brute-force initialisation of items that differ in set-up as one voting and one tail launch
+// (mpe_solve_bruteforce_batch_setups): item i runs with setups[item_setup[i]], both arrays and the block table
+// (mpe_brute_blocks.h) in device memory; max_markers sizes the dynamic LDS for the largest set-up of the call.  The
+// voting launch ADDS the strict arithmetic's votes (glibc's powers with vote_arith 3 / 4) to zeroed histograms; the
+// tail launch is k3a_validate<0> + k3b_refine_group<0> of every item in one block.
+hipError_t launch_k2_vote_setups(const mpe_detections* dets, const SolveParams* setups, const int* item_setup,
+                                 const BruteBlock* blocks, int n_blocks, int max_markers, int vote_arith, uint32_t* hist,
+                                 hipStream_t s);
+hipError_t launch_k3_tail_setups(const mpe_detections* dets, const uint32_t* hist, int n_items, const SolveParams* setups,
+                                 const int* item_setup, int max_markers, mpe_result* results, uint32_t* corr_out,
+                                 void* mid_buf, hipStream_t s);
 hipError_t launch_repack(const uint8_t* src, size_t src_stride, size_t src_frame_stride, int n_frames, int roi_x,
                          int roi_y, int roi_w, int roi_h, uint8_t* dst, int dst_pitch, hipStream_t s);
 

@@ -1605,6 +1605,38 @@ __global__ __launch_bounds__(K2_THREADS) void k2_vote_strict(const mpe_detection
   k2_strict_frame<false, GLIBC>(d, sp, hist + (size_t)f * MPE_HIST_STRIDE, f, part, splits, item_range, smem, s_px, s_iv, s_hist);
 }
 
+// The strict loop nest for items that differ in camera, marker set and parameters, in ONE launch
+// (mpe_solve_bruteforce_batch_setups): block b works on entry b of a block table built on the host
+// (mpe_brute_blocks.h) — share `part` of `parts` of item `item` — with the SolveParams of that item's set-up from a
+// table that came in the call's input copy, built by make_solve_params exactly as the kernel argument of
+// k2_vote_strict is, and ADDS its votes to the item's zeroed histogram.  The sum over an item's blocks is the
+// histogram k2_vote_strict gives that item, whatever the partition: the votes are integers.  The table entries are
+// block-uniform and read-only for the launch; they are addressed through the constant address space, as
+// k_track_frame's set-up table is (mpe_k3.hip track_setup), so that the uniform fields load as kernel arguments do.
+// No block is launched for an item that cannot vote; the test below repeats k2_vote_strict's for a table that names
+// one all the same (uniform over the block, in front of every barrier).
+template <bool GLIBC>
+__global__ __launch_bounds__(K2_THREADS) void k2_vote_setups(const mpe_detections* __restrict__ dets,
+                                                             const SolveParams* __restrict__ setups,
+                                                             const int* __restrict__ item_setup,
+                                                             const BruteBlock* __restrict__ blocks,
+                                                             uint32_t* __restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double s_px[MPE_MAX_DETECTIONS][2];
+  __shared__ double s_iv[MPE_MAX_DETECTIONS][3];
+  __shared__ unsigned s_hist[MPE_HIST_WORDS];
+  typedef __attribute__((address_space(4))) const SolveParams* ConstSetups;
+  typedef __attribute__((address_space(4))) const int* ConstInts;
+  ConstInts bb = (ConstInts)reinterpret_cast<const int*>(blocks + blockIdx.x);
+  const int item = bb[0], part = bb[1], parts = bb[2];
+  const int k = ((ConstInts)item_setup)[item];
+  const SolveParams& sp = *(const SolveParams*)((ConstSetups)setups + k);
+  const mpe_detections* d = dets + item;
+  if (d->n < 4 || d->status != 0 || sp.n_markers < 4) return;
+  k2_strict_frame<false, GLIBC>(d, sp, hist + (size_t)item * MPE_HIST_STRIDE, item, part, parts, nullptr, smem, s_px, s_iv,
+                                s_hist);
+}
+
 // Frames that lost a suspect entry to a full list (k2_sus_lost) are voted again, whole, with the strict loop nest: the
 // histogram is STORED over whatever the fast launch and the fix-up kernel left, the mark is cleared, the tail then
 // sees an ordinary frame.  Frames too WIDE for the fast kernels (more than MPE_FAST_VOTE_DETECTIONS detections; they
@@ -1871,6 +1903,23 @@ hipError_t launch_k2_vote(mpe_detections* dets, int n_frames, const SolveParams&
     }
 #undef MPE_K2_PLAIN
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_k2_vote_setups(const mpe_detections* dets, const SolveParams* setups, const int* item_setup,
+                                 const BruteBlock* blocks, int n_blocks, int max_markers, int vote_arith, uint32_t* hist,
+                                 hipStream_t s) {
+  if (n_blocks <= 0 || max_markers < 4) return hipSuccess;
+  // back-projection columns of the largest set-up, as launch_k2_vote sizes them for the strict kernel (16 markers: 52 KB
+  // beside 6.5 KB of static LDS, inside the 64 KB a block may have without an opt-in)
+  const int threads = K2_THREADS;
+  const size_t lds = (size_t)(max_markers - 3) * 2 * threads * sizeof(double);
+  if (vote_arith_glibc_pow(vote_arith))
+    hipLaunchKernelGGL(k2_vote_setups<true>, dim3((unsigned)n_blocks), dim3(threads), lds, s, dets, setups, item_setup,
+                       blocks, hist);
+  else
+    hipLaunchKernelGGL(k2_vote_setups<false>, dim3((unsigned)n_blocks), dim3(threads), lds, s, dets, setups, item_setup,
+                       blocks, hist);
   return hipGetLastError();
 }
 

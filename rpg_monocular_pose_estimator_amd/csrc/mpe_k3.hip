@@ -1166,6 +1166,38 @@ hipError_t launch_track_frames_setups(const TrackFramesArgs& t, int n_frames, co
   return hipGetLastError();
 }
 
+// The tail of brute-force items that differ in set-up, as ONE launch (mpe_solve_bruteforce_batch_setups): block b is
+// item b — correspondences from its vote histogram, validation (the body of k3a_validate<0>), a block barrier where the
+// launch boundary is, Kabsch + Gauss-Newton (the body of k3b_refine_group<0>) — with the SolveParams of the item's
+// set-up read from the call's table through the constant address space, as k_track_frame reads its set-up (track_setup
+// above).  One wave per block and no early exit: every thread reaches every barrier of the two bodies.  An item is
+// frame 0 of a launch of one frame, as a tracked frame is in k_track_frame: what a group of 16 lanes computes does not
+// depend on the block it sits in, so the records are those of launch_k3_tail over the items of one set-up.
+__global__ __launch_bounds__(64) void k3_tail_setups(const mpe_detections* __restrict__ dets,
+                                                     const uint32_t* __restrict__ hist,
+                                                     const SolveParams* __restrict__ setups,
+                                                     const int* __restrict__ item_setup, mpe_result* __restrict__ results,
+                                                     uint32_t* __restrict__ corr_out, TailMid* __restrict__ mid) {
+  typedef __attribute__((address_space(4))) const SolveParams* ConstSetups;
+  typedef __attribute__((address_space(4))) const int* ConstInts;
+  const int b = blockIdx.x;
+  const int k = ((ConstInts)item_setup)[b];
+  const SolveParams& sp = *(const SolveParams*)((ConstSetups)setups + k);
+  k3a_body<0>(dets + b, hist + (size_t)b * MPE_HIST_STRIDE, 1, sp, results + b, corr_out + (size_t)b * 2 * MPE_MAX_MARKERS,
+              nullptr, nullptr, 0.0, mid + b, 0);
+  __syncthreads();
+  k3b_group_body<0>(dets + b, 1, sp, results + b, mid + b, sp.n_markers > 3 ? sp.n_markers : 4, 0);
+}
+hipError_t launch_k3_tail_setups(const mpe_detections* dets, const uint32_t* hist, int n_items, const SolveParams* setups,
+                                 const int* item_setup, int max_markers, mpe_result* results, uint32_t* corr_out,
+                                 void* mid_buf, hipStream_t s) {
+  if (n_items <= 0) return hipSuccess;
+  const size_t lds_a = track_lds_bytes(max_markers);  // (every block lays its set-up's buffers out from the start)
+  hipLaunchKernelGGL(k3_tail_setups, dim3((unsigned)n_items), dim3(64), lds_a, s, dets, hist, setups, item_setup, results,
+                     corr_out, static_cast<TailMid*>(mid_buf));
+  return hipGetLastError();
+}
+
 hipError_t launch_k3_tail(const mpe_detections* dets, const uint32_t* hist, int n_frames, const SolveParams& sp,
                           mpe_result* results, uint32_t* corr_out, const uint32_t* corr_in, const double* nn_pred,
                           double nn_tol, void* mid_buf, hipStream_t s, int mode) {

@@ -285,6 +285,7 @@ int mpe_get_option(mpe_handle* h, const char* name, int* value) {
   else if (n == "track_batch_submits") *value = (int)h->track_batch_submits;
   else if (n == "track_batch_chains") *value = (int)h->track_batch_chains;
   else if (n == "track_batch_reruns") *value = (int)h->track_batch_reruns;
+  else if (n == "bruteforce_submits") *value = (int)h->bruteforce_submits;
   else if (n == "track_ns_pack") *value = (int)(h->track_ns[0] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_enqueue") *value = (int)(h->track_ns[1] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_wait") *value = (int)(h->track_ns[2] / std::max(1LL, h->track_steps));

@@ -32,6 +32,19 @@ int enter(mpe_handle* h) {
   return MPE_OK;
 }
 
+// the pinned staging memory (inputs out, records back) holds at least `need` bytes; what it held is lost when it grows
+int grow_mailbox(mpe_handle* h, size_t need) {
+  if (need <= h->mailbox_cap) return MPE_OK;
+  if (h->mailbox) (void)hipHostFree(h->mailbox);
+  h->mailbox = nullptr;
+  h->mailbox_cap = 0;
+  const size_t want = std::max(need + need / 4, (size_t)1 << 16);
+  const hipError_t e = hipHostMalloc(&h->mailbox, want, hipHostMallocDefault);
+  if (e != hipSuccess) return fail(h, MPE_ERR_HIP, "hipHostMalloc (staging memory)", e);
+  h->mailbox_cap = want;
+  return MPE_OK;
+}
+
 unsigned factorial_u32(int n) {  // combinations.cpp:34-40: 32-bit wrap-around kept on purpose
   unsigned r = 1;
   for (int i = 2; i <= n; ++i) r *= (unsigned)i;

@@ -31,18 +31,6 @@ bool roi_inside(const mpe_track_item& it, int rows, int cols) {
          it.roi_y + it.roi_h <= rows;
 }
 
-// the pinned staging memory (inputs out, records back) holds at least `need` bytes; what it held is lost when it grows
-int grow_mailbox(mpe_handle* h, size_t need) {
-  if (need <= h->mailbox_cap) return MPE_OK;
-  if (h->mailbox) (void)hipHostFree(h->mailbox);
-  h->mailbox = nullptr;
-  h->mailbox_cap = 0;
-  const size_t want = std::max(need + need / 4, (size_t)1 << 16);
-  HIP_TRY(h, hipHostMalloc(&h->mailbox, want, hipHostMallocDefault));
-  h->mailbox_cap = want;
-  return MPE_OK;
-}
-
 // the ROI of `it` into a g.rows x g.pitch slot, zero beyond it
 void pack_roi(uint8_t* slot, const FrameGeom& g, const mpe_track_item& it, size_t stride_bytes) {
   for (int y = 0; y < g.rows; ++y) {

@@ -650,32 +650,60 @@ struct BatchCtx {
     return MPE_OK;
   }
 
-  // brute-force (re-)initialisations requested so far: one submission per set-up that has any
+  // brute-force (re-)initialisations requested so far, in ONE submission: the lanes of one set-up through
+  // mpe_solve_bruteforce_batch, the lanes of two or more set-ups through mpe_solve_bruteforce_batch_setups (with a
+  // set-up without markers among them: one call per set-up, as it was)
   int brute() {
+    int n_with = 0;
+    bool all_have_markers = true;  // (the _setups entry refuses a set-up without markers; alone it just finds no pose)
+    std::vector<char> has(setups.size(), 0);
+    for (int i = 0; i < n; ++i) {
+      const size_t s = (size_t)lane_setup[(size_t)i];
+      if (L[(size_t)i].op != OP_BRUTE || has[s]) continue;
+      has[s] = 1;
+      ++n_with;
+      all_have_markers = all_have_markers && setups[s].n_markers >= 1;
+    }
+    if (n_with >= 2 && all_have_markers) return brute_setup(-1);
     for (size_t s = 0; s < setups.size(); ++s) {
+      if (!has[s]) continue;
       const int rc = brute_setup((int)s);
       if (rc != MPE_OK) return rc;
     }
     return MPE_OK;
   }
+  // setup >= 0: the OP_BRUTE lanes of that set-up; -1: those of every set-up
   int brute_setup(int setup) {
     std::vector<int> idx;
     for (int i = 0; i < n; ++i)
-      if (L[(size_t)i].op == OP_BRUTE && lane_setup[(size_t)i] == setup) idx.push_back(i);
+      if (L[(size_t)i].op == OP_BRUTE && (setup < 0 || lane_setup[(size_t)i] == setup)) idx.push_back(i);
     if (idx.empty()) return MPE_OK;
-    const mpe_tracker* t0 = ts[idx[0]];  // (the set-up of these lanes)
     const int m = (int)idx.size();
     std::vector<double> det_xy((size_t)m * 2 * MPE_MAX_DETECTIONS, 0.0);
-    std::vector<int> nd((size_t)m);
+    std::vector<int> nd((size_t)m), su((size_t)m), slot_of(setups.size(), -1);
+    std::vector<mpe_track_setup> bsetups;
     for (int k = 0; k < m; ++k) {
       const mpe_tracker* t = ts[idx[(size_t)k]];
       nd[(size_t)k] = (int)t->det.size() / 2;
+      const int s = lane_setup[(size_t)idx[(size_t)k]];
+      if (setup < 0 && slot_of[(size_t)s] < 0) {  // the set-ups that have such lanes, in order of first appearance
+        slot_of[(size_t)s] = (int)bsetups.size();
+        bsetups.push_back(setups[(size_t)s]);
+      }
+      su[(size_t)k] = setup < 0 ? slot_of[(size_t)s] : 0;
       std::memcpy(&det_xy[(size_t)k * 2 * MPE_MAX_DETECTIONS], t->det.data(), t->det.size() * sizeof(double));
     }
     res.resize((size_t)m);
     std::vector<uint32_t> hist((size_t)m * MPE_MAX_DETECTIONS * MPE_MAX_MARKERS), bc((size_t)m * 2 * MPE_MAX_MARKERS);
-    const int rc = mpe_solve_bruteforce_batch(h, det_xy.data(), nd.data(), m, t0->markers.data(), n_markers(t0), t0->K,
-                                              &t0->p, res.data(), hist.data(), bc.data());
+    int rc;
+    if (setup >= 0) {
+      const mpe_tracker* t0 = ts[idx[0]];  // (the set-up of these lanes)
+      rc = mpe_solve_bruteforce_batch(h, det_xy.data(), nd.data(), m, t0->markers.data(), n_markers(t0), t0->K, &t0->p,
+                                      res.data(), hist.data(), bc.data());
+    } else {
+      rc = mpe_solve_bruteforce_batch_setups(h, det_xy.data(), nd.data(), su.data(), m, bsetups.data(), (int)bsetups.size(),
+                                             res.data(), hist.data(), bc.data());
+    }
     if (rc != MPE_OK) return rc;
     for (int k = 0; k < m; ++k) {
       const int i = idx[(size_t)k];

@@ -12,4 +12,10 @@ for t in tests/test_k1b_host.py tests/test_geometry_host.py tests/test_ddmath_ho
     python -m pytest $t -x -q -p no:cacheprovider -s "$@" 2>&1 | grep -E "runtime error|ERROR: AddressSanitizer|passed|failed|error" || true
   [ ${PIPESTATUS[0]} -ne 0 ] && rc=1
 done
+# the block table of the mixed-set-up brute-force launch (csrc/mpe_brute_blocks.h): a stand-alone program with its own
+# main, linked against the sanitizer runtimes itself
+BB=$(mktemp -d)/brute_blocks_host
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+    -I rpg_monocular_pose_estimator_amd/csrc tests/host/brute_blocks_host.cpp -o $BB && $BB || rc=1
+rm -rf "$(dirname $BB)"
 exit $rc
