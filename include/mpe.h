@@ -382,6 +382,27 @@ int mpe_track_step_batch_setups_device(mpe_handle* h, const mpe_track_item* item
 int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
                                               int rows, int cols, size_t stride_bytes, const mpe_track_setup* setups,
                                               int n_setups);
+/* mpe_track_step_batch_setups_device[_submit] for device frames in the camera's own ENCODING (a decoder or a DMA engine
+ * that delivers bgr8, mono16, ... into device memory): `encoding` is one MPE_ENC_* value for the whole call, as rows,
+ * cols and the stride are; src_big_endian has the meaning it has in mpe_convert_to_mono8 (read for MPE_ENC_MONO16
+ * alone).  stride_bytes is in SOURCE bytes (Image.step); rows, cols and every ROI stay in pixels; items[i].img needs no
+ * alignment.  The gather kernel decodes the pixels it gathers, by the rules stated at mpe_convert_to_mono8, so no mono8
+ * copy of the frames is made and no separate conversion is launched: every detection record, correspondence row and
+ * result is byte-identical to what mpe_track_step_batch_setups_device returns over the same frames after
+ * mpe_convert_to_mono8 with a device destination (and so to the host entries' records over the converted frames).
+ * MPE_ENC_MONO8 is handed to mpe_track_step_batch_setups_device_submit as it is.  mpe_track_step_batch_collect / _cancel
+ * serve this submit too; ordering as above.  Usage errors, all before any device work: whatever
+ * mpe_track_step_batch_setups_device_submit refuses (every img must lie, with its whole ENCODED image —
+ * (rows - 1) * stride_bytes + cols * bytes per pixel —, inside one device allocation on the handle's device);
+ * stride_bytes < cols * bytes per pixel: MPE_ERR_ARG; an encoding outside the six (Bayer, YUV): MPE_ERR_UNSUPPORTED, as
+ * mpe_convert_to_mono8 answers it. */
+int mpe_track_step_batch_setups_device_encoded(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                                               int rows, int cols, size_t stride_bytes, int encoding, int src_big_endian,
+                                               const mpe_track_setup* setups, int n_setups, mpe_detections* dets_out,
+                                               uint32_t* corr_out, mpe_result* out);
+int mpe_track_step_batch_setups_device_encoded_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup,
+                                                      int n, int rows, int cols, size_t stride_bytes, int encoding,
+                                                      int src_big_endian, const mpe_track_setup* setups, int n_setups);
 /* mpe_solve_bruteforce for N detection sets in one submission (the re-initialisations of a lock-step batch):
  * det_xy n x MPE_MAX_DETECTIONS x 2 (n_det[i] valid rows); hist (optional) n x MPE_MAX_DETECTIONS x
  * MPE_MAX_MARKERS, corr (optional) n x 2*MPE_MAX_MARKERS. */
@@ -486,6 +507,20 @@ int mpe_tracker_run_sequences_batch_device_threads(mpe_tracker* const* trackers,
                                                    int n_frames, int rows, int cols, size_t stride_bytes,
                                                    size_t frame_stride_bytes, const double* times, mpe_result* out,
                                                    int* info, int n_threads);
+/* The two entries above for device frames in the camera's own encoding (MPE_ENC_*, one value per call; src_big_endian
+ * for MPE_ENC_MONO16; stride_bytes and frame_stride_bytes in SOURCE bytes, rows and cols in pixels): the detections go
+ * through mpe_track_step_batch_setups_device_encoded_submit, the whole-image ones (a cold first step, a retry) as well —
+ * the gather then decodes the whole frame.  Records and info are byte-identical to those of the entries above over
+ * the same frames after mpe_convert_to_mono8.  An encoding outside the six is MPE_ERR_UNSUPPORTED, a stride below
+ * cols * bytes per pixel MPE_ERR_ARG, both before any tracker is touched. */
+int mpe_tracker_estimate_batch_device_encoded(mpe_tracker* const* trackers, int n, const uint8_t* const* d_imgs, int rows,
+                                              int cols, size_t stride_bytes, int encoding, int src_big_endian,
+                                              const double* times, mpe_result* out, int* info, int* updated);
+int mpe_tracker_run_sequences_batch_device_encoded_threads(mpe_tracker* const* trackers, int n,
+                                                           const uint8_t* const* d_frames, int n_frames, int rows, int cols,
+                                                           size_t stride_bytes, size_t frame_stride_bytes, int encoding,
+                                                           int src_big_endian, const double* times, mpe_result* out,
+                                                           int* info, int n_threads);
 
 /* The estimator's private state (pose_estimator.h:56-62, 74-79), for callers that drive the public
  * step methods of the class (predictPose, findCorrespondences, ... — see compat/) between calls of

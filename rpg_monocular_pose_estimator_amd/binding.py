@@ -98,7 +98,7 @@ def source_fingerprint():
     hsh = hashlib.sha256()
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
-                                  "mpe_gather.h", "mpe_brute_blocks.h"):
+                                  "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -207,6 +207,15 @@ def load_library():
     lib.mpe_track_step_batch_setups_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                                        C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mpe_track_step_batch_setups_device_submit.argtypes = lib.mpe_track_step_batch_setups_device.argtypes[:9]
+    # ... in the camera's own encoding: (encoding, src_big_endian) behind the stride(s)
+    enc = [C.c_int, C.c_int]
+    a = lib.mpe_track_step_batch_setups_device.argtypes
+    lib.mpe_track_step_batch_setups_device_encoded.argtypes = a[:7] + enc + a[7:]
+    lib.mpe_track_step_batch_setups_device_encoded_submit.argtypes = a[:7] + enc + a[7:9]
+    a = lib.mpe_tracker_estimate_batch.argtypes
+    lib.mpe_tracker_estimate_batch_device_encoded.argtypes = a[:6] + enc + a[6:]
+    a = lib.mpe_tracker_run_sequences_batch_threads.argtypes
+    lib.mpe_tracker_run_sequences_batch_device_encoded_threads.argtypes = a[:8] + enc + a[8:]
     lib.mpe_shard_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mpe_shard_bounds.restype = None
     lib.mpe_estimate_batch_multi.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
@@ -217,9 +226,10 @@ def load_library():
     return lib
 
 
-def _estimate_batch(name, trackers, ptrs, rows, cols, stride, times):
+def _estimate_batch(name, trackers, ptrs, rows, cols, stride, times, enc=()):
     """One lock-step time step through entry `name`: ptrs = the trackers' images (host or device addresses) of one
-    shape and row stride.  -> (records (N), info (N,8), updated (N) bool)."""
+    shape and row stride; enc: (encoding, big_endian) for an *_encoded entry.
+    -> (records (N), info (N,8), updated (N) bool)."""
     lib = load_library()
     n = len(trackers)
     ts = (C.c_void_p * n)(*[t._t for t in trackers])
@@ -227,24 +237,25 @@ def _estimate_batch(name, trackers, ptrs, rows, cols, stride, times):
     rec = np.zeros(n, RESULT_DTYPE)
     info = np.zeros((n, 8), np.int32)
     upd = np.zeros(n, np.int32)
-    rc = getattr(lib, name)(ts, n, ptrs, rows, cols, stride, _dp(times), rec.ctypes.data, info.ctypes.data,
+    rc = getattr(lib, name)(ts, n, ptrs, rows, cols, stride, *enc, _dp(times), rec.ctypes.data, info.ctypes.data,
                             upd.ctypes.data)
     if rc < 0:
         raise MpeError("%s failed (%d): %s" % (name, rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
     return rec, info, upd.astype(bool)
 
 
-def _run_sequences_batch(name, trackers, ptrs, n, rows, cols, stride, fstride, times, threads):
+def _run_sequences_batch(name, trackers, ptrs, n, rows, cols, stride, fstride, times, threads, enc=()):
     """The lock-step loop in C through entry `name`: ptrs = the trackers' sequences (host or device addresses) of n
-    frames each, one shape, row stride and frame stride.  -> (records (N,n), info (N,n,8))."""
+    frames each, one shape, row stride and frame stride; enc: (encoding, big_endian) for an *_encoded entry.
+    -> (records (N,n), info (N,n,8))."""
     lib = load_library()
     N = len(trackers)
     ts = (C.c_void_p * N)(*[t._t for t in trackers])
     times = _f64(times).reshape(-1)
     rec = np.zeros((N, n), RESULT_DTYPE)
     info = np.zeros((N, n, 8), np.int32)
-    rc = getattr(lib, name)(ts, N, ptrs, n, rows, cols, stride, fstride, _dp(times), rec.ctypes.data, info.ctypes.data,
-                            int(threads))
+    rc = getattr(lib, name)(ts, N, ptrs, n, rows, cols, stride, fstride, *enc, _dp(times), rec.ctypes.data,
+                            info.ctypes.data, int(threads))
     if rc < 0:
         raise MpeError("%s failed (%d): %s" % (name, rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
     return rec, info
@@ -290,42 +301,73 @@ def tracker_run_sequences_batch_mixed(trackers, frames, times, threads=1):
     return tracker_run_sequences_batch(trackers, frames, times, threads, mixed=True)
 
 
-def _device_images(imgs, lead):
-    """The streams' images in device memory: a list of torch uint8 CUDA tensors, one per stream, or one tensor with a
-    leading stream dimension; `lead` dimensions in front of (rows, cols).  All on one device, pixels contiguous within
-    a row, the same strides.  Work queued on torch's current stream of that device is waited for (the frames must be
-    final when they are submitted).  -> (the tensors — keep them alive across the call —, device pointers, shape,
-    strides in bytes)."""
+def _device_images(imgs, lead, encoding="mono8"):
+    """The streams' images in device memory: a list of torch CUDA tensors, one per stream, or one tensor with a leading
+    stream dimension; `lead` dimensions in front of the image.  mono8: (rows, cols) uint8.  Any other encoding
+    (ENCODINGS): (rows, cols, bytes per pixel) uint8 with the bytes of a pixel contiguous, or, mono16, (rows, cols)
+    uint16 / int16.  All on one device, pixels contiguous within a row, the same strides; row stride and storage offset
+    are free.  Work queued on torch's current stream of that device is waited for (the frames must be final when they
+    are submitted).  -> (the tensors — keep them alive across the call —, device pointers, the lead + (rows, cols)
+    shape, their strides in BYTES)."""
     import torch
+    if encoding not in ENCODINGS:
+        raise MpeError("encoding %r: one of %s" % (encoding, ", ".join(sorted(ENCODINGS))))
+    bpp = {"mono8": 1, "mono16": 2, "bgr8": 3, "rgb8": 3}.get(encoding, 4)
     ts = list(imgs.unbind(0)) if _is_torch(imgs) else list(imgs)
     t0 = ts[0]
     for t in ts:
-        if not (_is_torch(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == lead + 2 and t.stride(-1) == 1):
-            raise MpeError("device frames: torch uint8 CUDA tensors with contiguous rows are needed (host frames: the host entries)")
-        if t.shape != t0.shape or t.stride() != t0.stride() or t.device != t0.device:
+        ok = _is_torch(t) and t.is_cuda
+        if ok and bpp == 1:
+            ok = t.dtype == torch.uint8 and t.dim() == lead + 2 and t.stride(-1) == 1
+        elif ok and t.dtype == torch.uint8:    # the bytes of a pixel as a last dimension
+            ok = t.dim() == lead + 3 and t.shape[-1] == bpp and t.stride(-1) == 1 and t.stride(-2) == bpp
+        elif ok:
+            ok = bpp == 2 and t.dtype in (torch.uint16, torch.int16) and t.dim() == lead + 2 and t.stride(-1) == 1
+        if not ok:
+            raise MpeError("device frames: torch CUDA tensors with contiguous rows are needed — (rows, cols) uint8 for mono8, "
+                           "(rows, cols, bytes per pixel) uint8 or, mono16, (rows, cols) uint16 / int16 for the other "
+                           "encodings (host frames: the host entries)")
+        if t.shape != t0.shape or t.stride() != t0.stride() or t.device != t0.device or t.dtype != t0.dtype:
             raise MpeError("device frames: every stream needs the same shape, strides and device")
     torch.cuda.current_stream(t0.device).synchronize()
-    return ts, (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), tuple(t0.shape), tuple(t0.stride())
+    es = t0.element_size()
+    return (ts, (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), tuple(t0.shape[:lead + 2]),
+            tuple(s * es for s in t0.stride()[:lead + 2]))
 
 
-def tracker_estimate_batch_device(trackers, imgs, times):
+def _enc_args(encoding, big_endian):
+    return (ENCODINGS[encoding], int(bool(big_endian)))
+
+
+def tracker_estimate_batch_device(trackers, imgs, times, encoding="mono8", big_endian=False):
     """mpe_tracker_estimate_batch_device: tracker_estimate_batch[_mixed] for frames that are in device memory — imgs: a
     list of (rows, cols) torch uint8 CUDA tensors, one per tracker, or one (N, rows, cols) tensor, on the device of the
     trackers' handle.  The trackers may mix set-ups.  -> (records (N), info (N,8), updated (N) bool), those of the host
-    entries over the same frames."""
-    keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0)  # (keep: the tensors stay alive across the call)
+    entries over the same frames.
+    encoding other than "mono8" (ENCODINGS; big_endian for "mono16"): mpe_tracker_estimate_batch_device_encoded over
+    frames in that encoding — (rows, cols, bytes per pixel) uint8 or, mono16, (rows, cols) uint16 / int16 tensors; the
+    records are those of the mono8 call over the frames after Handle.convert_to_mono8."""
+    keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0, encoding)  # (keep: alive across the call)
     assert len(keep) == len(trackers)
-    return _estimate_batch("mpe_tracker_estimate_batch_device", trackers, ptrs, rows, cols, stride, times)
+    if encoding == "mono8":
+        return _estimate_batch("mpe_tracker_estimate_batch_device", trackers, ptrs, rows, cols, stride, times)
+    return _estimate_batch("mpe_tracker_estimate_batch_device_encoded", trackers, ptrs, rows, cols, stride, times,
+                           _enc_args(encoding, big_endian))
 
 
-def tracker_run_sequences_batch_device(trackers, frames, times, threads=1):
+def tracker_run_sequences_batch_device(trackers, frames, times, threads=1, encoding="mono8", big_endian=False):
     """mpe_tracker_run_sequences_batch_device_threads: tracker_run_sequences_batch[_mixed] over sequences that are in
     device memory — frames: a list of (n, rows, cols) torch uint8 CUDA tensors, one per tracker, or one (N, n, rows, cols)
-    tensor.  Each handle's trackers form one lock-step group that may mix set-ups.  -> (records (N,n), info (N,n,8))."""
-    keep, ptrs, (n, rows, cols), (fstride, stride, _) = _device_images(frames, 1)  # (keep: alive across the call)
+    tensor.  Each handle's trackers form one lock-step group that may mix set-ups.  -> (records (N,n), info (N,n,8)).
+    encoding other than "mono8": mpe_tracker_run_sequences_batch_device_encoded_threads over sequences in that encoding
+    ((n, rows, cols, bytes per pixel) uint8 or, mono16, (n, rows, cols) uint16 / int16), as tracker_estimate_batch_device."""
+    keep, ptrs, (n, rows, cols), (fstride, stride, _) = _device_images(frames, 1, encoding)  # (keep: alive across the call)
     assert len(keep) == len(trackers)
-    return _run_sequences_batch("mpe_tracker_run_sequences_batch_device_threads", trackers, ptrs, n, rows, cols, stride,
-                                fstride, times, threads)
+    if encoding == "mono8":
+        return _run_sequences_batch("mpe_tracker_run_sequences_batch_device_threads", trackers, ptrs, n, rows, cols, stride,
+                                    fstride, times, threads)
+    return _run_sequences_batch("mpe_tracker_run_sequences_batch_device_encoded_threads", trackers, ptrs, n, rows, cols,
+                                stride, fstride, times, threads, _enc_args(encoding, big_endian))
 
 
 class TrackItem(C.Structure):  # mpe_track_item
@@ -727,7 +769,7 @@ class Handle:
                     undist=np.array(det.undist_xy[:2 * n]).reshape(-1, 2), gn_iterations=res.gn_iterations)
 
     # ---- one lock-step time step of N streams: mpe_track_step_batch_setups[_device] ----------------------
-    def _track_step_batch(self, entry, ptrs, rows, cols, stride, rois, predicted_px, setups, item_setup):
+    def _track_step_batch(self, entry, ptrs, rows, cols, stride, rois, predicted_px, setups, item_setup, enc=()):
         n = len(ptrs)
         keep = []
         su = (TrackSetup * len(setups))()
@@ -744,7 +786,7 @@ class Handle:
         idx = None if item_setup is None else (C.c_int * n)(*[int(v) for v in item_setup])
         dets, corr = np.zeros(n, DETECTIONS_DTYPE), np.zeros((n, MAX_MARKERS, 2), np.uint32)
         res = np.zeros(n, RESULT_DTYPE)
-        rc = getattr(self._lib, entry)(self._h, items, idx, n, rows, cols, C.c_size_t(stride), su, len(setups),
+        rc = getattr(self._lib, entry)(self._h, items, idx, n, rows, cols, C.c_size_t(stride), *enc, su, len(setups),
                                        C.c_void_p(dets.ctypes.data), C.c_void_p(corr.ctypes.data),
                                        C.c_void_p(res.ctypes.data))
         self._check(rc, entry)
@@ -761,13 +803,20 @@ class Handle:
         return self._track_step_batch("mpe_track_step_batch_setups", [im.ctypes.data for im in imgs], rows, cols, stride,
                                       rois, predicted_px, setups, item_setup)
 
-    def track_step_batch_device(self, imgs, rois, predicted_px, setups, item_setup=None):
+    def track_step_batch_device(self, imgs, rois, predicted_px, setups, item_setup=None, encoding="mono8", big_endian=False):
         """mpe_track_step_batch_setups_device: track_step_batch for frames in device memory.  imgs: a list of N
         (rows, cols) torch uint8 CUDA tensors on this handle's device (any common row stride), or one (N, rows, cols)
-        tensor; item_setup None: one set-up for all.  Same records as track_step_batch over the same frames."""
-        keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0)
-        out = self._track_step_batch("mpe_track_step_batch_setups_device", list(ptrs), rows, cols, stride, rois,
-                                     predicted_px, setups, item_setup)
+        tensor; item_setup None: one set-up for all.  Same records as track_step_batch over the same frames.
+        encoding other than "mono8" (ENCODINGS; big_endian for "mono16"): mpe_track_step_batch_setups_device_encoded
+        over frames in that encoding — (rows, cols, bytes per pixel) uint8 or, mono16, (rows, cols) uint16 / int16
+        tensors; rois stay in pixels.  Same records as the mono8 call over the frames after convert_to_mono8."""
+        keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0, encoding)
+        if encoding == "mono8":
+            out = self._track_step_batch("mpe_track_step_batch_setups_device", list(ptrs), rows, cols, stride, rois,
+                                         predicted_px, setups, item_setup)
+        else:
+            out = self._track_step_batch("mpe_track_step_batch_setups_device_encoded", list(ptrs), rows, cols, stride, rois,
+                                         predicted_px, setups, item_setup, _enc_args(encoding, big_endian))
         del keep
         return out
 

@@ -7,9 +7,16 @@
 // dwords that are funnel-shifted into place.  No load touches a byte outside the image [img, img + img_bytes): the
 // dword that straddles the first or the last byte of the image is put together from byte loads of the bytes the
 // segment wants, and a dword the segment wants nothing of is not loaded.
+//
+// gather_segment_encoded is the same segment for frames in the camera's own encoding (k_gather_rois_encoded): the 16
+// slot bytes are 16 PIXELS of the ROI row, decoded from 2 (mono16), 3 (bgr8 / rgb8) or 4 (bgra8 / rgba8) source bytes
+// each by the rules of mpe_pixel.h — the bytes mpe_convert_to_mono8 would have written into a mono8 copy of the frame.
+// x, y, w, h stay in pixels; stride and img_bytes are source bytes.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include "mpe_pixel.h"
 
 #ifndef __host__
 #define __host__
@@ -75,6 +82,77 @@ __host__ __device__ inline void gather_segment(const Loads& mem, const uint8_t* 
     const uint32_t v = (uint32_t)(((((uint64_t)d[i + 1]) << 32) | d[i]) >> (8 * sh));
     const int valid = n - 4 * i;  // bytes of this dword inside the ROI row
     out[i] = valid >= 4 ? v : (valid <= 0 ? 0u : v & ((1u << (8 * valid)) - 1u));
+  }
+}
+
+// pixels [16 * seg, 16 * seg + 16) of slot row r, decoded from BPP source bytes each -> out[0..3] (little endian).
+// img_bytes: the image ends with the last pixel of its last row, (rows - 1) * stride + cols * BPP.  rgb: the colour
+// pixels are R G B [A] (else B G R [A]); big_endian: the mono16 values are (BPP 2 alone reads it).
+template <int BPP, class Loads>
+__host__ __device__ inline void gather_segment_encoded(const Loads& mem, const uint8_t* img, size_t img_bytes, size_t stride,
+                                                       int x, int y, int w, int h, int r, int seg, bool rgb, bool big_endian,
+                                                       uint32_t out[4]) {
+  static_assert(BPP == 2 || BPP == 3 || BPP == 4, "mono16, bgr8 / rgb8, bgra8 / rgba8");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  const int c0 = 16 * seg;
+  if (r >= h || c0 >= w) return;
+  const int n = w - c0 < 16 ? w - c0 : 16;  // pixels wanted
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(img), hi = lo + img_bytes;
+  const uintptr_t src = lo + (size_t)(y + r) * stride + (size_t)(x + c0) * BPP, end = src + (size_t)n * BPP;
+  const unsigned sh = (unsigned)(src & 3);
+  const uintptr_t base = src - sh;  // aligned; up to 3 bytes in front of src (and of the image)
+  constexpr int ND = 4 * BPP;       // source dwords of 16 pixels
+  uint32_t d[ND + 1];
+#pragma unroll
+  for (int j = 0; j < ND + 1; ++j) {
+    const uintptr_t a = base + 4 * (uintptr_t)j;
+    uint32_t v = 0;
+    if (a < end) {
+      if (a >= lo && a + 4 <= hi) {
+        v = mem.ld32(a);
+      } else {  // the dword straddles an end of the image: the wanted bytes of it, one by one
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (a + b >= src && a + b < end) v |= mem.ld8(a + b) << (8 * b);
+      }
+    }
+    d[j] = v;
+  }
+  uint32_t s[ND];  // the source bytes from src on
+#pragma unroll
+  for (int i = 0; i < ND; ++i) s[i] = (uint32_t)(((((uint64_t)d[i + 1]) << 32) | d[i]) >> (8 * sh));
+  unsigned px[16];
+  if constexpr (BPP == 2) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      unsigned a = s[k] & 0xFFFFu, b = s[k] >> 16;
+      if (big_endian) {
+        a = ((a & 0xFFu) << 8) | (a >> 8);
+        b = ((b & 0xFFu) << 8) | (b >> 8);
+      }
+      px[2 * k] = mono16_px(a);
+      px[2 * k + 1] = mono16_px(b);
+    }
+  } else if constexpr (BPP == 3) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {  // four pixels in three dwords
+      const uint32_t w0 = s[3 * q], w1 = s[3 * q + 1], w2 = s[3 * q + 2];
+      px[4 * q] = gray_px(w0 & 0xFF, (w0 >> 8) & 0xFF, (w0 >> 16) & 0xFF, rgb);
+      px[4 * q + 1] = gray_px(w0 >> 24, w1 & 0xFF, (w1 >> 8) & 0xFF, rgb);
+      px[4 * q + 2] = gray_px((w1 >> 16) & 0xFF, w1 >> 24, w2 & 0xFF, rgb);
+      px[4 * q + 3] = gray_px((w2 >> 8) & 0xFF, (w2 >> 16) & 0xFF, w2 >> 24, rgb);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) px[k] = gray_px(s[k] & 0xFF, (s[k] >> 8) & 0xFF, (s[k] >> 16) & 0xFF, rgb);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (4 * i + b < n) v |= px[4 * i + b] << (8 * b);  // (pixels beyond the ROI row hold whatever lay behind it)
+    out[i] = v;
   }
 }
 

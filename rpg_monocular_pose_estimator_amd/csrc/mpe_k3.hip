@@ -3,6 +3,7 @@
 #include "mpe_kernels_common.h"
 #include "mpe_k2_head.h"
 #include "mpe_k1b_dev.h"  // (the blob extraction's device functions: k_track_frame below runs a whole tracked frame)
+#include "mpe_pixel.h"    // (gray_px, mono16_px: the per-pixel conversion of k_to_mono8, shared with the encoded ROI gather)
 namespace mpe {
 //@file-prologue-end
 // =============================================================================================
@@ -1285,15 +1286,8 @@ __global__ __launch_bounds__(64) void k_quartic_batch(const double* __restrict__
 // =============================================================================================
 // frame decode: sensor_msgs/Image payloads -> mono8 (what cv_bridge::toCvCopy(msg, MONO8) does for the node,
 // monocular_pose_estimator.cpp:147).  HBM bound, one pass: 4 output pixels per lane and step.
-//   bgr8 / rgb8 / bgra8 / rgba8: cv::cvtColor(..., COLOR_*2GRAY) for CV_8U — integer, 14 fractional bits,
-//       Y = (B * 1868 + G * 9617 + R * 4899 + 2^13) >> 14   (OpenCV 2.4, 3.0 .. 3.4.1; from 3.4.2 on: 15 bits, see mpe.h)
-//   mono16 (host byte order after cv_bridge's endianness fix): Mat::convertTo(CV_8U, 255. / 65535.) —
-//       saturate_cast<uchar>((float)v * (float)(255. / 65535.)), i.e. round-half-even of the single-precision product
+// The per-pixel rules (gray_px for bgr8 / rgb8 / bgra8 / rgba8, mono16_px for mono16) are in mpe_pixel.h.
 // =============================================================================================
-__device__ __forceinline__ unsigned gray_px(unsigned c0, unsigned c1, unsigned c2, bool rgb) {
-  const unsigned b = rgb ? c2 : c0, r = rgb ? c0 : c2;
-  return (b * 1868u + c1 * 9617u + r * 4899u + (1u << 13)) >> 14;
-}
 __global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ src, size_t src_stride, size_t src_frame_stride,
                                                   int encoding, int big_endian, int rows, int cols, long long n_rows_total,
                                                   uint8_t* __restrict__ dst) {
@@ -1312,9 +1306,7 @@ __global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ sr
       for (int k = 0; k < n; ++k) {
         const uint8_t* p = s + 2 * (size_t)(x0 + k);
         const unsigned v = big_endian ? ((unsigned)p[0] << 8 | p[1]) : ((unsigned)p[1] << 8 | p[0]);
-        float r = rintf((float)v * (float)(255.0 / 65535.0));
-        r = fminf(fmaxf(r, 0.f), 255.f);
-        out[k] = (unsigned)r;
+        out[k] = mono16_px(v);
       }
     } else if (encoding == MPE_ENC_MONO8) {
       for (int k = 0; k < n; ++k) out[k] = s[x0 + k];

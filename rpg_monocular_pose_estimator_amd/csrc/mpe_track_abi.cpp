@@ -1,8 +1,9 @@
 // mpe_track_abi.cpp — host side of libmpe_hip.so, part 3 (see mpe_host.h): one tracked frame (mpe_track_step) and the
-// lock-step time step of N camera streams (mpe_track_step_batch[_setups][_device][_submit / _collect / _cancel]); the
+// lock-step time step of N camera streams (mpe_track_step_batch[_setups][_device[_encoded]][_submit / _collect / _cancel]); the
 // per-stream state machine on top of them is mpe_tracker.cpp.  Every entry checks its own arguments and then makes the
 // same submission (submit_slots): a uniform batch is the submission of one set-up, a tracked frame a batch of one, and
-// frames in device memory differ only in where the ROI slots come from (a gather kernel instead of a host copy).
+// frames in device memory differ only in where the ROI slots come from (a gather kernel instead of a host copy; for
+// frames in the camera's own encoding, a gather kernel that decodes).
 #include "mpe_host.h"
 #include "mpe_gather.h"
 
@@ -141,13 +142,16 @@ int track_range_chain(mpe_handle* h, const mpe_handle::PendingTrack::Range& r, i
 // them.  Where the pixels are is the one thing that varies: host frames are packed into the staging memory (pack_roi)
 // and travel with the header; of device frames (img_bytes each: an image ends with the last pixel of its last row) the
 // header carries a gather table instead and k_gather_rois writes the same slot bytes on the device, in front of
-// everything that reads them.  The caller has checked the arguments and entered the handle.
-enum PixelSource { kHostFrames, kDeviceFrames };
+// everything that reads them; of device frames in the camera's own encoding (bgr8 .. mono16; stride_bytes and img_bytes
+// in source bytes, the ROIs in pixels) k_gather_rois_encoded writes them, decoding what it gathers — the slots are mono8
+// whatever the source was, so nothing behind the gather, the overflow re-run in _collect included, knows the encoding.
+// The caller has checked the arguments and entered the handle.
+enum PixelSource { kHostFrames, kDeviceFrames, kEncodedDeviceFrames };
 
 int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, const FrameGeom& g,
                  size_t stride_bytes, const TrackSetup* setups, int n_setups, PixelSource source = kHostFrames,
-                 size_t img_bytes = 0) {
-  const bool on_device = source == kDeviceFrames;
+                 size_t img_bytes = 0, int encoding = MPE_ENC_MONO8, int big_endian = 0) {
+  const bool on_device = source != kHostFrames;
   mpe_handle::PendingTrack& pt = h->pending_track;
   pt.t_in = h->track_profile ? clk::now() : clk::time_point();
   auto setup_of = [item_setup](int i) { return item_setup ? item_setup[i] : 0; };
@@ -234,9 +238,12 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   pt.d_pred = reinterpret_cast<const double*>(d_in);
   pt.d_wins = d_in + pred_bytes;
   pt.d_pix = d_in + head_bytes;
-  if (on_device)
+  if (source == kDeviceFrames)
     HIP_TRY(h, launch_gather_rois(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g, stride_bytes,
                                   img_bytes, h->stream));
+  else if (source == kEncodedDeviceFrames)
+    HIP_TRY(h, launch_gather_rois_encoded(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g,
+                                          stride_bytes, img_bytes, encoding, big_endian, h->stream));
   ++h->track_batch_submits;
   // round 6: the fused ranges as ONE launch, a block per stream (k_track_frame), the records stored to the pinned
   // staging memory by the kernel (track_fused 2) — scan, small blob tier, tail and copy-out were five commands, and
@@ -361,6 +368,40 @@ int mpe_track_step_batch_setups_device(mpe_handle* h, const mpe_track_item* item
                                        mpe_detections* dets_out, uint32_t* corr_out, mpe_result* out) {
   if (!dets_out || !corr_out || !out) return fail(h, MPE_ERR_ARG, "bad argument");
   const int rc = mpe_track_step_batch_setups_device_submit(h, items, item_setup, n, rows, cols, stride_bytes, setups, n_setups);
+  if (rc != MPE_OK) return rc;
+  if (n == 0) return MPE_OK;  // (nothing was submitted)
+  return mpe_track_step_batch_collect(h, dets_out, corr_out, out);
+}
+
+int mpe_track_step_batch_setups_device_encoded_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup,
+                                                      int n, int rows, int cols, size_t stride_bytes, int encoding,
+                                                      int src_big_endian, const mpe_track_setup* setups, int n_setups) {
+  // every usage error before any device work: those of mpe_track_step_batch_setups_device_submit, and the encoding
+  if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || rows < 1 || cols < 1)
+    return fail(h, MPE_ERR_ARG, "bad argument");
+  const size_t bpp = (size_t)encoding_bytes_per_pixel(encoding);
+  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+  if (stride_bytes < (size_t)cols * bpp) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (encoding == MPE_ENC_MONO8)  // nothing to decode: the mono8 submission and k_gather_rois
+    return mpe_track_step_batch_setups_device_submit(h, items, item_setup, n, rows, cols, stride_bytes, setups, n_setups);
+  FrameGeom g;
+  std::vector<TrackSetup> prep;
+  int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
+  if (rc != MPE_OK || n == 0) return rc;
+  ENTER(h);
+  const size_t img_bytes = (size_t)(rows - 1) * stride_bytes + (size_t)cols * bpp;
+  if ((rc = check_device_images(h, items, n, img_bytes)) != MPE_OK) return rc;
+  return submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups, kEncodedDeviceFrames, img_bytes,
+                      encoding, src_big_endian ? 1 : 0);
+}
+
+int mpe_track_step_batch_setups_device_encoded(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                                               int rows, int cols, size_t stride_bytes, int encoding, int src_big_endian,
+                                               const mpe_track_setup* setups, int n_setups, mpe_detections* dets_out,
+                                               uint32_t* corr_out, mpe_result* out) {
+  if (!dets_out || !corr_out || !out) return fail(h, MPE_ERR_ARG, "bad argument");
+  const int rc = mpe_track_step_batch_setups_device_encoded_submit(h, items, item_setup, n, rows, cols, stride_bytes, encoding,
+                                                                   src_big_endian, setups, n_setups);
   if (rc != MPE_OK) return rc;
   if (n == 0) return MPE_OK;  // (nothing was submitted)
   return mpe_track_step_batch_collect(h, dets_out, corr_out, out);

@@ -1,7 +1,9 @@
 // mpe_track_device.hip — the ROI gather of lock-step submissions whose frames are in DEVICE memory
 // (mpe_track_step_batch_setups_device[_submit]): submit_slots (mpe_track_abi.cpp) does not pack the ROI slots on the
 // host and copy them, k_gather_rois writes them from the caller's device images.  The slot bytes are those pack_roi
-// writes, so everything behind them is the host-frame submission's.
+// writes, so everything behind them is the host-frame submission's.  k_gather_rois_encoded does the same for frames in
+// the camera's own encoding (mpe_track_step_batch_setups_device_encoded[_submit]): it decodes the pixels it gathers, so
+// no mono8 copy of the frames is made first.
 #include "mpe_host.h"
 #include "mpe_gather.h"
 
@@ -27,6 +29,30 @@ __global__ __launch_bounds__(256) void k_gather_rois(const GatherItem* __restric
       make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+// The same slots from ENCODED images (BPP source bytes per pixel: 2 mono16, 3 bgr8 / rgb8, 4 bgra8 / rgba8): one thread
+// per 16 pixels of a slot row = 16 * BPP source bytes as aligned dwords (consecutive lanes read consecutive runs of an
+// image row), decoded by the rules of mpe_pixel.h, one 16-byte store.  The dword array of a segment (4 * BPP + 1) is
+// indexed by unrolled loops alone and stays in registers.
+template <int BPP>
+__global__ __launch_bounds__(256) void k_gather_rois_encoded(const GatherItem* __restrict__ tab, int n,
+                                                             uint8_t* __restrict__ dst, size_t slot_bytes, int rows,
+                                                             int segs_per_row, size_t stride, size_t img_bytes, int rgb,
+                                                             int big_endian) {
+  const size_t segs_per_slot = (size_t)rows * segs_per_row;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)n * segs_per_slot) return;
+  const int e = (int)(idx / segs_per_slot);
+  const int rem = (int)(idx - (size_t)e * segs_per_slot);
+  const int r = rem / segs_per_row, seg = rem - r * segs_per_row;
+  const GatherItem it = tab[e];
+  uint32_t o[4];
+  gather_segment_encoded<BPP>(GatherLoads(), it.img, img_bytes, stride, it.x, it.y, it.w, it.h, r, seg, rgb != 0,
+                              big_endian != 0, o);
+  // (slot base, pitch and segment offset are multiples of 16)
+  *reinterpret_cast<uint4*>(dst + (size_t)it.slot * slot_bytes + ((size_t)r * segs_per_row + seg) * 16) =
+      make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 }  // namespace
 
 namespace mpe_host {
@@ -38,6 +64,33 @@ hipError_t launch_gather_rois(const GatherItem* tab, int n, uint8_t* dst, const 
   if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_gather_rois, dim3((unsigned)blocks), dim3(256), 0, s, tab, n, dst, (size_t)g.rows * g.pitch, g.rows,
                      g.segs_per_row, stride, img_bytes);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_rois_encoded(const GatherItem* tab, int n, uint8_t* dst, const FrameGeom& g, size_t stride,
+                                      size_t img_bytes, int encoding, int big_endian, hipStream_t s) {
+  const size_t total = (size_t)n * g.rows * g.segs_per_row;
+  const size_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  const int rgb = encoding == MPE_ENC_RGB8 || encoding == MPE_ENC_RGBA8;
+  const dim3 grid((unsigned)blocks), block(256);
+  const size_t slot_bytes = (size_t)g.rows * g.pitch;
+  switch (encoding_bytes_per_pixel(encoding)) {
+    case 2:
+      hipLaunchKernelGGL(k_gather_rois_encoded<2>, grid, block, 0, s, tab, n, dst, slot_bytes, g.rows, g.segs_per_row, stride,
+                         img_bytes, 0, big_endian);
+      break;
+    case 3:
+      hipLaunchKernelGGL(k_gather_rois_encoded<3>, grid, block, 0, s, tab, n, dst, slot_bytes, g.rows, g.segs_per_row, stride,
+                         img_bytes, rgb, 0);
+      break;
+    case 4:
+      hipLaunchKernelGGL(k_gather_rois_encoded<4>, grid, block, 0, s, tab, n, dst, slot_bytes, g.rows, g.segs_per_row, stride,
+                         img_bytes, rgb, 0);
+      break;
+    default:  // (mono8 goes through launch_gather_rois; anything else was refused by the entry)
+      return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/mpe.h"
+#include "mpe_pixel.h"  // (encoding_bytes_per_pixel)
 
 namespace mpe_host {
 void set_error(mpe_handle* h, const char* what);  // the text of mpe_last_error (mpe_options.cpp)
@@ -496,6 +497,8 @@ struct BatchCtx {
   // different set-ups on one handle; otherwise every lane must have the first one's.
   bool mixed = false;
   bool frames_on_device = false;  // imgs are device pointers (the *_device entries): the device-frame submission
+  int encoding = MPE_ENC_MONO8;   // of device frames (the *_device_encoded entries): the gather decodes; stride in source bytes
+  int big_endian = 0;             // ... their mono16 values are big-endian
   std::vector<mpe_track_setup> setups;
   std::vector<int> lane_setup, item_setup;
 
@@ -584,8 +587,13 @@ struct BatchCtx {
       pend.push_back(i);
     }
     if (items.empty()) return 0;
-    const int rc = (frames_on_device ? mpe_track_step_batch_setups_device_submit : mpe_track_step_batch_setups_submit)(
-        h, items.data(), item_setup.data(), (int)items.size(), rows, cols, stride, setups.data(), (int)setups.size());
+    // (MPE_ENC_MONO8: the encoded entry hands the call to mpe_track_step_batch_setups_device_submit)
+    const int rc = frames_on_device
+                       ? mpe_track_step_batch_setups_device_encoded_submit(h, items.data(), item_setup.data(), (int)items.size(),
+                                                                           rows, cols, stride, encoding, big_endian,
+                                                                           setups.data(), (int)setups.size())
+                       : mpe_track_step_batch_setups_submit(h, items.data(), item_setup.data(), (int)items.size(), rows, cols,
+                                                            stride, setups.data(), (int)setups.size());
     if (rc != MPE_OK) {
       pend.clear();
       return rc;
@@ -808,9 +816,24 @@ mpe_tracker::~mpe_tracker() { delete solo; }
 
 extern "C" {
 
+// the encoding of device frames, before a tracker's state is touched (the submission would refuse it as well, but only
+// after begin() has advanced the prediction): the codes of mpe_track_step_batch_setups_device_encoded_submit
+static int check_encoding(mpe_handle* h, int encoding, int cols, size_t stride_bytes) {
+  const int bpp = mpe::encoding_bytes_per_pixel(encoding);
+  if (!bpp) {
+    mpe_host::set_error(h, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+    return MPE_ERR_UNSUPPORTED;
+  }
+  if (encoding != MPE_ENC_MONO8 && (cols < 1 || stride_bytes < (size_t)cols * (size_t)bpp)) {
+    mpe_host::set_error(h, "bad argument");
+    return MPE_ERR_ARG;
+  }
+  return MPE_OK;
+}
+
 static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
                           size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated, bool mixed,
-                          bool on_device = false) {
+                          bool on_device = false, int encoding = MPE_ENC_MONO8, int big_endian = 0) {
   if (!ts || n < 0 || !imgs || !times) return MPE_ERR_ARG;
   if (n == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -818,7 +841,10 @@ static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* i
   BatchCtx c;
   int rc = c.validate(ts, n, mixed);
   if (rc != MPE_OK) return rc;
+  if ((rc = check_encoding(c.h, encoding, cols, stride_bytes)) != MPE_OK) return rc;
   c.frames_on_device = on_device;
+  c.encoding = encoding;
+  c.big_endian = big_endian;
   c.begin(imgs, rows, cols, stride_bytes, times);
   if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
     c.cancel();  // (a submission may still be in flight: leave the handle usable)
@@ -863,6 +889,14 @@ int mpe_tracker_estimate_batch_device(mpe_tracker* const* ts, int n, const uint8
   return estimate_batch(ts, n, d_imgs, rows, cols, stride_bytes, times, out, info, updated, true, true);
 }
 
+// the frames in device memory in the camera's own encoding: the ROI gather decodes them (stride_bytes in source bytes)
+int mpe_tracker_estimate_batch_device_encoded(mpe_tracker* const* ts, int n, const uint8_t* const* d_imgs, int rows, int cols,
+                                              size_t stride_bytes, int encoding, int src_big_endian, const double* times,
+                                              mpe_result* out, int* info, int* updated) {
+  return estimate_batch(ts, n, d_imgs, rows, cols, stride_bytes, times, out, info, updated, true, true, encoding,
+                        src_big_endian ? 1 : 0);
+}
+
 // The lock-step loops of N streams over recorded sequences.  Trackers that live on DIFFERENT handles form groups
 // (one group per handle, each with the same camera / marker / parameter set inside the group); the groups are
 // pipelined against each other: while the device works on step k of one group, the host collects, advances and
@@ -870,7 +904,8 @@ int mpe_tracker_estimate_batch_device(mpe_tracker* const* ts, int n, const uint8
 // (mixed: each group may mix cameras, marker sets and parameters — mpe_tracker_run_sequences_batch_mixed_threads)
 static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows, int cols,
                                size_t stride_bytes, size_t frame_stride_bytes, const double* times, mpe_result* out,
-                               int* info, int n_threads, bool mixed, bool on_device = false) {
+                               int* info, int n_threads, bool mixed, bool on_device = false, int encoding = MPE_ENC_MONO8,
+                               int big_endian = 0) {
   if (!ts || n < 0 || !frames || !times || n_frames < 0 || n_threads < 1) return MPE_ERR_ARG;
   if (n == 0 || n_frames == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -899,6 +934,12 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
     const int rc = ctx[g].validate(gts[g].data(), (int)gts[g].size(), mixed);
     if (rc != MPE_OK) return rc;
     ctx[g].frames_on_device = on_device;
+    ctx[g].encoding = encoding;
+    ctx[g].big_endian = big_endian;
+  }
+  for (size_t g = 0; g < G; ++g) {
+    const int rc = check_encoding(hs[g], encoding, cols, stride_bytes);
+    if (rc != MPE_OK) return rc;
   }
   // The groups gs[0..) on the calling thread, pipelined against each other: while the device works on step k of one
   // group, the host collects, advances and packs another.  Groups share nothing (own handle, own trackers, own rows
@@ -988,6 +1029,15 @@ int mpe_tracker_run_sequences_batch_device_threads(mpe_tracker* const* ts, int n
                                                    int* info, int n_threads) {
   return run_sequences_batch(ts, n, d_frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
                              n_threads, true, true);
+}
+
+// ... in the camera's own encoding (stride_bytes and frame_stride_bytes in source bytes)
+int mpe_tracker_run_sequences_batch_device_encoded_threads(mpe_tracker* const* ts, int n, const uint8_t* const* d_frames,
+                                                           int n_frames, int rows, int cols, size_t stride_bytes,
+                                                           size_t frame_stride_bytes, int encoding, int src_big_endian,
+                                                           const double* times, mpe_result* out, int* info, int n_threads) {
+  return run_sequences_batch(ts, n, d_frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
+                             n_threads, true, true, encoding, src_big_endian ? 1 : 0);
 }
 
 int mpe_tracker_run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows,
