@@ -9,6 +9,10 @@
 //   facade_selftest framepath < encoding names
 //       which of the node's three frame paths (in place / back-end decode / cv_bridge) each encoding takes, in the
 //       default build and in the MPE_OPENCV_GRAY_14BIT build (host only)
+//   facade_selftest wide --markers <yaml> --camera "fx fy cx cy" [--dist "k1 k2 p1 p2 k3"] [--points <file> --tol t]
+//                        [--frame <file.raw> --rows R --cols C --frame-tol t]
+//       setWideFrames off and on: setImagePoints + initialise + optimiseAndUpdatePose on a point set of 65 .. 256 points,
+//       estimateBodyPose on a frame with that many blobs; prints the exception or the rows, pose and covariance
 //   facade_selftest steps --markers <yaml> --frames <file.raw> --rows R --cols C [--dt s] [--overlay-out file.bgr]
 //       object A: estimateBodyPose per frame.  object B: the same state machine written out with the
 //       class's public step methods exactly as pose_estimator.cpp:62-147 strings them together
@@ -181,6 +185,102 @@ int main(int argc, char** argv) {
       const FramePath p0 = framePathForEncoding(name, false, &e0);
       const FramePath p1 = framePathForEncoding(name, true, &e1);
       std::printf("%s %d %d %d %d\n", name, (int)p0, e0, (int)p1, e1);
+    }
+    return 0;
+  }
+  if (argc >= 2 && !std::strcmp(argv[1], "wide")) {
+    // setWideFrames: a point set and / or a frame of 65 .. 256 detections through the class, switch off and on
+    const char *markers = 0, *points = 0, *frame = 0;
+    int rows = 0, cols = 0;
+    double cam[4] = {0, 0, 0, 0}, dist[5] = {0, 0, 0, 0, 0}, tol = 5, frame_tol = 5;
+    for (int i = 2; i + 1 < argc; i += 2) {
+      if (!std::strcmp(argv[i], "--markers")) markers = argv[i + 1];
+      else if (!std::strcmp(argv[i], "--points")) points = argv[i + 1];
+      else if (!std::strcmp(argv[i], "--frame")) frame = argv[i + 1];
+      else if (!std::strcmp(argv[i], "--rows")) rows = std::atoi(argv[i + 1]);
+      else if (!std::strcmp(argv[i], "--cols")) cols = std::atoi(argv[i + 1]);
+      else if (!std::strcmp(argv[i], "--tol")) tol = std::atof(argv[i + 1]);
+      else if (!std::strcmp(argv[i], "--frame-tol")) frame_tol = std::atof(argv[i + 1]);
+      else if (!std::strcmp(argv[i], "--camera")) std::sscanf(argv[i + 1], "%lf %lf %lf %lf", cam, cam + 1, cam + 2, cam + 3);
+      else if (!std::strcmp(argv[i], "--dist")) std::sscanf(argv[i + 1], "%lf %lf %lf %lf %lf", dist, dist + 1, dist + 2, dist + 3, dist + 4);
+    }
+    List4DPoints pts;
+    if (!markers || !read_markers(markers, pts) || (!points && !frame)) return 2;
+    auto setup = [&](PoseEstimator& pe, bool wide, double t) {
+      configure(pe);
+      pe.camera_matrix_K_(0, 0) = cam[0];
+      pe.camera_matrix_K_(1, 1) = cam[1];
+      pe.camera_matrix_K_(0, 2) = cam[2];
+      pe.camera_matrix_K_(1, 2) = cam[3];
+      pe.camera_distortion_coeffs_.assign(dist, dist + 5);
+      pe.setBackProjectionPixelTolerance(t);
+      pe.setMarkerPositions(pts);
+      pe.setWideFrames(wide);
+    };
+    auto print_state = [](const char* what, PoseEstimator& pe) {
+      std::printf("%s rows", what);
+      const VectorXuPairs c = pe.getCorrespondences();
+      for (size_t i = 0; i < c.size(); ++i) std::printf(" %u %u", c[i][0], c[i][1]);
+      std::printf("\n%s pose", what);
+      const Matrix4d T = pe.getPredictedPose();
+      for (int i = 0; i < 16; ++i) std::printf(" %.17g", T(i));
+      std::printf("\n%s cov", what);
+      const Matrix6d C = pe.getPoseCovariance();
+      for (int i = 0; i < 36; ++i) std::printf(" %.17g", C(i));
+      std::printf("\n");
+    };
+    try {
+      if (points) {
+        List2DPoints det;
+        std::FILE* fp = std::fopen(points, "r");
+        if (!fp) return 2;
+        double x, y;
+        while (std::fscanf(fp, "%lf %lf", &x, &y) == 2) {
+          Vector2d p;
+          p(0) = x;
+          p(1) = y;
+          det.push_back(p);
+        }
+        std::fclose(fp);
+        for (int wide = 0; wide < 2; ++wide) {
+          PoseEstimator pe;
+          setup(pe, wide != 0, tol);
+          pe.setImagePoints(det);
+          try {
+            const unsigned ok = pe.initialise();
+            std::printf("points wide=%d initialise %u\n", wide, ok);
+            if (ok == 1) {
+              double t = 0.0;
+              pe.optimiseAndUpdatePose(t);
+              print_state("points", pe);
+            }
+          } catch (const std::exception& e) {
+            std::printf("points wide=%d exception %s\n", wide, e.what());
+          }
+        }
+      }
+      if (frame) {
+        std::vector<uint8_t> buf((size_t)rows * cols);
+        std::FILE* fp = std::fopen(frame, "rb");
+        if (!fp || std::fread(buf.data(), 1, buf.size(), fp) != buf.size()) return 2;
+        std::fclose(fp);
+        const ImageView img(buf.data(), rows, cols, (size_t)cols);
+        for (int wide = 0; wide < 2; ++wide) {
+          PoseEstimator pe;
+          setup(pe, wide != 0, frame_tol);
+          try {
+            const bool ok = pe.estimateBodyPose(img, 0.25);
+            std::printf("frame wide=%d estimateBodyPose %d points %d centres %d\n", wide, (int)ok, (int)pe.getImagePoints().size(),
+                        (int)pe.getDistortedDetectionCenters().size());
+            if (ok) print_state("frame", pe);
+          } catch (const std::exception& e) {
+            std::printf("frame wide=%d exception %s\n", wide, e.what());
+          }
+        }
+      }
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "error: %s\n", e.what());
+      return 3;
     }
     return 0;
   }

@@ -13,7 +13,7 @@ static void check(mpe_handle* h, int rc, const char* what) {
 PoseEstimator::PoseEstimator()
     : detection_threshold_value_(0), gaussian_sigma_(0), min_blob_area_(0), max_blob_area_(0),
       max_width_height_distortion_(0), max_circular_distortion_(0), roi_border_thickness_(0), handle_(0),
-      tracker_(0), bruteforce_every_frame_(false), current_time_(0), previous_time_(0), predicted_time_(0),
+      tracker_(0), bruteforce_every_frame_(false), wide_frames_(false), current_time_(0), previous_time_(0), predicted_time_(0),
       it_since_initialized_(0), pose_updated_(false) {
   mpe_default_params(&params_);
   params_.back_projection_pixel_tolerance = 3;    // pose_estimator.cpp:36
@@ -174,8 +174,38 @@ unsigned PoseEstimator::checkCorrespondences() {
   return 1;
 }
 
+mpe_result PoseEstimator::solveWide() {
+  std::vector<double> det((size_t)2 * MPE_WIDE_DETECTIONS, 0.0);
+  const int n = (int)image_points_.size(), n_m = (int)(markers_xyz_.size() / 3);
+  for (int i = 0; i < n; ++i) {
+    det[2 * i] = image_points_[i](0);
+    det[2 * i + 1] = image_points_[i](1);
+  }
+  mpe_result res;
+  std::vector<uint32_t> corr(2 * MPE_MAX_MARKERS, 0u), hist((size_t)MPE_WIDE_DETECTIONS * MPE_MAX_MARKERS, 0u);
+  check(handle_, mpe_solve_bruteforce_batch_wide(handle_, det.data(), &n, 1, markers_xyz_.data(), n_m,
+                                                 camera_matrix_K_.data(), &params_, &res, hist.data(), corr.data()),
+        "mpe_solve_bruteforce_batch_wide");
+  bool any_vote = false;
+  for (size_t i = 0; i < hist.size(); ++i) any_vote = any_vote || hist[i] != 0;
+  if (any_vote) {  // pose_estimator.cpp:704-706: correspondences_ is only rewritten when the histogram has votes
+    correspondences_.clear();
+    for (int i = 0; i < res.n_corr; ++i) correspondences_.push_back({{corr[2 * i], corr[2 * i + 1]}});
+  }
+  return res;
+}
+
 unsigned PoseEstimator::initialise() {
   syncParams();
+  if (wideCount()) {
+    // 65 .. 256 image points with setWideFrames(true): the wide brute-force entry.  Its pose is already refined (the
+    // entry has no unrefined form); the optimisePose() that follows starts from it and stays within its convergence.
+    const mpe_result res = solveWide();
+    if (res.status != MPE_FRAME_POSE) return 0;
+    for (int i = 0; i < 16; ++i) predicted_pose_(i) = res.T[i];
+    pushState();
+    return 1;
+  }
   const std::vector<double> det = flatImagePoints();
   const int n_m = (int)(markers_xyz_.size() / 3);
   mpe_result res;
@@ -199,11 +229,25 @@ unsigned PoseEstimator::initialise() {
 
 void PoseEstimator::optimisePose() {
   syncParams();
-  const std::vector<double> det = flatImagePoints();
-  const std::vector<uint32_t> corr = flatCorrespondences();
+  std::vector<double> det = flatImagePoints();
+  std::vector<uint32_t> corr = flatCorrespondences();
+  int n_det = (int)image_points_.size();
+  if (wideCount()) {
+    // optimisePose reads only the detections its rows name (pose_estimator.cpp:733-792): hand over those, re-indexed
+    std::vector<double> named;
+    for (size_t i = 0; i < correspondences_.size(); ++i) {
+      const uint32_t d = corr[2 * i + 1];
+      if (d < 1 || d > (uint32_t)n_det) throw std::runtime_error("optimisePose: correspondence index out of range");
+      named.push_back(det[2 * (d - 1)]);
+      named.push_back(det[2 * (d - 1) + 1]);
+      corr[2 * i + 1] = (uint32_t)i + 1;
+    }
+    det.swap(named);
+    n_det = (int)correspondences_.size();
+  }
   mpe_result res;
   check(handle_,
-        mpe_optimise_pose(handle_, det.data(), (int)image_points_.size(), markers_xyz_.data(),
+        mpe_optimise_pose(handle_, det.data(), n_det, markers_xyz_.data(),
                           (int)(markers_xyz_.size() / 3), camera_matrix_K_.data(), &params_, corr.data(),
                           (int)correspondences_.size(), predicted_pose_.data(), &res),
         "mpe_optimise_pose");
@@ -264,6 +308,41 @@ bool PoseEstimator::estimateBodyPose(const ImageView& image, double time_to_pred
   predicted_time_ = time_to_predict;
   mpe_result r;
   const int rc = mpe_tracker_estimate(tracker_, image.data, image.rows, image.cols, image.step, time_to_predict, &r, 0);
+  if (rc == MPE_FRAME_TOO_MANY_DETECTIONS && wide_frames_ && (bruteforce_every_frame_ || it_since_initialized_ < 1)) {
+    // the uninitialised branch (pose_estimator.cpp:68-91) on a frame with more than 64 blobs: whole-image detection with
+    // the 256-point record, then the wide brute-force initialisation + refinement; state as optimiseAndUpdatePose leaves it
+    pullState();
+    mpe_detections_wide dw;
+    check(handle_, mpe_detect_batch_wide(handle_, image.data, 1, image.rows, image.cols, image.step,
+                                         (size_t)image.rows * image.step, 0, camera_matrix_K_.data(), D,
+                                         (int)camera_distortion_coeffs_.size(), &params_, &dw),
+          "mpe_detect_batch_wide");
+    if (dw.status < 0) throw std::runtime_error("mpe_detect_batch_wide: frame exceeded a device capacity");
+    image_points_.resize(dw.n);
+    distorted_detection_centers_.resize(dw.n);
+    for (int i = 0; i < dw.n; ++i) {
+      image_points_[i](0) = dw.undist_xy[2 * i];
+      image_points_[i](1) = dw.undist_xy[2 * i + 1];
+      distorted_detection_centers_[i].x = dw.dist_xy[2 * i];
+      distorted_detection_centers_[i].y = dw.dist_xy[2 * i + 1];
+    }
+    region_of_interest_ = Rect(0, 0, image.cols, image.rows);
+    predicted_pixel_positions_.clear();
+    pose_updated_ = false;
+    const mpe_result res = solveWide();
+    if (res.status == MPE_FRAME_POSE) {
+      for (int i = 0; i < 16; ++i) predicted_pose_(i) = res.T[i];
+      for (int i = 0; i < 36; ++i) pose_covariance_(i) = res.cov[i];
+      if (it_since_initialized_ < 2) it_since_initialized_++;
+      previous_pose_ = current_pose_;
+      current_pose_ = predicted_pose_;
+      previous_time_ = current_time_;
+      current_time_ = predicted_time_;
+      pose_updated_ = true;
+    }
+    pushState();
+    return pose_updated_;
+  }
   if (rc < 0) throw std::runtime_error(std::string("mpe_tracker_estimate: ") + mpe_last_error(handle_));
   pose_updated_ = rc == 1;
   double xy[2 * MPE_MAX_DETECTIONS];

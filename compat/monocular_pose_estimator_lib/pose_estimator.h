@@ -53,6 +53,12 @@ class PoseEstimator {
   //! OpenCV calls throw cv::Exception in the same situations), returns pose_updated_ otherwise
   bool estimateBodyPose(const ImageView& image, double time_to_predict);
   void setBruteForceEveryFrame(bool on) { bruteforce_every_frame_ = on; }  //!< extension, see header comment
+  //! Extension, default off: with it on, initialise() and the uninitialised branch of estimateBodyPose take the wide
+  //! entries of include/mpe.h (mpe_detect_batch_wide, mpe_solve_bruteforce_batch_wide) for 65 .. MPE_WIDE_DETECTIONS
+  //! detections in place of the capacity exception, and optimisePose() hands the refinement only the detections the
+  //! correspondences name.  Off, nothing changes.  The tracked branch keeps its 64-point records either way.
+  void setWideFrames(bool on) { wide_frames_ = on; }
+  bool getWideFrames() const { return wide_frames_; }
 
   void setPredictedTime(double time) {
     predicted_time_ = time;
@@ -121,6 +127,11 @@ class PoseEstimator {
   mpe_handle* handle_;
   mpe_tracker* tracker_;
   bool bruteforce_every_frame_;
+  bool wide_frames_;
+  bool wideCount() const { return wide_frames_ && image_points_.size() > (size_t)MPE_MAX_DETECTIONS &&
+                                  image_points_.size() <= (size_t)MPE_WIDE_DETECTIONS; }
+  //! setImagePoints + initialise + optimisePose of the wide path on image_points_: fills correspondences_, returns the record
+  mpe_result solveWide();
   mpe_params params_;
   std::vector<double> markers_xyz_;
   Matrix4d current_pose_, previous_pose_, predicted_pose_;

@@ -33,10 +33,13 @@ extern "C" {
 
 #define MPE_MAX_MARKERS 16    /* object_points_ capacity (reference: unbounded; 32-bit factorial
                                  already overflows at 13, COMB.cpp:34-45 — replicated) */
-#define MPE_MAX_DETECTIONS 64 /* detections kept per frame; more -> status MPE_FRAME_TOO_MANY_DETECTIONS.  (The
-                                 reference has no limit, led_detector.cpp:65-86 / pose_estimator.cpp:549-557; with 64
-                                 detections and 5 markers initialise() already runs 2.5 M P3P solves for one frame.
-                                 Frames with more than MPE_FAST_VOTE_DETECTIONS are voted by the strict loop nest.) */
+#define MPE_MAX_DETECTIONS 64 /* detections kept per frame by the ordinary entries; more -> status
+                                 MPE_FRAME_TOO_MANY_DETECTIONS.  (The reference has no limit, led_detector.cpp:65-86 /
+                                 pose_estimator.cpp:549-557; with 64 detections and 5 markers initialise() already runs
+                                 2.5 M P3P solves for one frame.  Frames with more than MPE_FAST_VOTE_DETECTIONS are voted
+                                 by the strict loop nest.)  Detection sets of up to MPE_WIDE_DETECTIONS go through the
+                                 separate *_wide entries below (mpe_vote_batch_wide, mpe_solve_bruteforce_batch_wide). */
+#define MPE_WIDE_DETECTIONS 256 /* detections of one set in the *_wide entries (= MPE_MAX_RAW_BLOBS) */
 #define MPE_FAST_VOTE_DETECTIONS 32 /* widest frame the fast voting kernels' 32-bit detection masks hold */
 #define MPE_MAX_RAW_BLOBS 256 /* external contours per frame before the shape filter */
 #define MPE_MAX_KSIZE 37      /* Gaussian kernel taps: sigma <= 6 (cfg:13) */
@@ -95,6 +98,14 @@ typedef struct mpe_detections {
   double undist_xy[2 * MPE_MAX_DETECTIONS]; /* pixel_positions of findLeds (LED.h:84-88); entries 2 n .. are unspecified */
   float dist_xy[2 * MPE_MAX_DETECTIONS];    /* distorted_detection_centers; entries 2 n .. are unspecified */
 } mpe_detections;
+
+/* mpe_detections with room for MPE_WIDE_DETECTIONS points: the record of the *_wide entries */
+typedef struct mpe_detections_wide {
+  int n;      /* min(number of detections, MPE_WIDE_DETECTIONS) */
+  int status; /* 0 or MPE_FRAME_TOO_MANY_* */
+  double undist_xy[2 * MPE_WIDE_DETECTIONS]; /* entries 2 n .. are unspecified */
+  float dist_xy[2 * MPE_WIDE_DETECTIONS];    /* entries 2 n .. are unspecified */
+} mpe_detections_wide;
 
 /* fills *p with the parameter set of launch/demo.launch:12-22 */
 void mpe_default_params(mpe_params* p);
@@ -424,6 +435,64 @@ int mpe_solve_bruteforce_batch(mpe_handle* h, const double* det_xy, const int* n
 int mpe_solve_bruteforce_batch_setups(mpe_handle* h, const double* det_xy, const int* n_det, const int* item_setup, int n,
                                       const mpe_track_setup* setups, int n_setups, mpe_result* out, uint32_t* hist,
                                       uint32_t* corr);
+
+/* ---- detection sets of 65 .. MPE_WIDE_DETECTIONS points (a glare frame: more than MPE_MAX_DETECTIONS blobs pass the
+ * shape filter).  The reference has no limit (pose_estimator.cpp:549-557 votes for any image_points_.size()); the
+ * ordinary entries refuse n_det > MPE_MAX_DETECTIONS.  A separate surface: no ordinary entry, record or status changes.
+ * Row strides are MPE_WIDE_DETECTIONS here, and detection indices (1-based, up to 256) are uint32 throughout.
+ *
+ * mpe_vote_batch_wide ≙ mpe_vote_batch (initialise()'s loop nest, pose_estimator.cpp:565-702) for 0 .. MPE_WIDE_DETECTIONS
+ * detections per set: det_xy n_frames x MPE_WIDE_DETECTIONS x 2, n_det[f] valid rows; hist n_frames x MPE_WIDE_DETECTIONS x
+ * MPE_MAX_MARKERS.  Always the strict arithmetic (one block per 1024 hypotheses of a set, spread over the chip): with
+ * vote_arith 3 / 4 the histograms of 4 / 3, with 1 / 0 those of 0 / 1 — for a set of up to MPE_MAX_DETECTIONS points the
+ * rows mpe_vote_batch returns.  vote_arith 2 (the fast arithmetic alone) has no strict form: MPE_ERR_UNSUPPORTED.
+ *
+ * mpe_solve_bruteforce_batch_wide ≙ mpe_solve_bruteforce_batch (setImagePoints + initialise + optimiseAndUpdatePose,
+ * pose_estimator.cpp:80-91,544-721,733-812): det_xy n x MPE_WIDE_DETECTIONS x 2; hist (optional) n x MPE_WIDE_DETECTIONS x
+ * MPE_MAX_MARKERS; corr (optional) n x 2*MPE_MAX_MARKERS, rows (marker, detection) with the detection's index in the
+ * caller's set (1 .. 256).  One submission for any n: one input copy, one memset, the wide voting launch, a small kernel
+ * that runs the all-zero test (pose_estimator.cpp:704) and correspondencesFromHistogram (:344-370) and hands the at most
+ * n_markers detections those rows name — all that checkCorrespondences and optimisePose read (:394-542, 733-792) — to
+ * the validate / refine kernels of mpe_check_and_refine, one copy back.  Status and record as mpe_solve_bruteforce: 1
+ * with the identity pose and zero covariance when the histogram is all zero, fewer than 4 detections or markers are
+ * given or the rows are rejected; out[i].n_det = n_det[i].
+ *
+ * Both: n == 0: MPE_OK.  MPE_ERR_ARG before any device work: null pointers, n_det[i] outside 0 .. MPE_WIDE_DETECTIONS,
+ * n_markers outside 1 .. MPE_MAX_MARKERS, a lock-step or streaming submission of the handle not collected yet.
+ * get "wide_frames": detection sets of more than MPE_MAX_DETECTIONS points mpe_solve_bruteforce_batch_wide has solved
+ * since the handle was made (see mpe_estimate_batch_wide).
+ * set "wide_block_cap" (tests): blocks per set of the wide voting launch at most (0 = automatic, four per compute unit);
+ * the histograms do not depend on it.
+ *
+ * mpe_detect_batch_wide ≙ mpe_detect_batch (LEDDetector::findLeds, led_detector.cpp:35-112, which loops over every
+ * contour) with records of MPE_WIDE_DETECTIONS points: the image scan and the general blob tier (its LDS-resident kernel
+ * with option "general_lds" 1) over every frame of the call — kept blobs and order (descending raster order of the
+ * contour's start pixel) as that tier computes them for mpe_detect_batch, only the cut-off moves from 64 to 256.  A frame
+ * that still exceeds a capacity keeps the code mpe_detect_batch gives it: a frame on which 257 blobs (or any number above
+ * 256) pass the filter gets MPE_FRAME_TOO_MANY_DETECTIONS (-10) with n = 256 and the first 256 of the reference's order
+ * (unless more than 512 passed: which blobs it then holds is unspecified, as for the narrow record); bright rows beyond
+ * the band capacity: MPE_FRAME_TOO_MANY_ROWS (-12).  MPE_FRAME_TOO_MANY_BLOBS (-11) is not produced by this tier — it
+ * counts the blobs that PASS, not the raw contours.
+ *
+ * mpe_estimate_batch_wide ≙ mpe_estimate_batch, arguments and all: it runs mpe_estimate_batch, then takes every frame
+ * whose record says MPE_FRAME_TOO_MANY_DETECTIONS through mpe_detect_batch_wide (one call per such frame: they are rare)
+ * and all of them through ONE mpe_solve_bruteforce_batch_wide, and overwrites those records; every other record is byte
+ * for byte what mpe_estimate_batch wrote.  A frame beyond the wide capacities keeps its code.  Under vote_arith 2 the call
+ * answers MPE_ERR_UNSUPPORTED only when a frame needs the wide solve (the records of mpe_estimate_batch are then in
+ * `results`); a batch without such a frame is mpe_estimate_batch.  "wide_frames" counts the
+ * frames solved this way (and, for direct callers of mpe_solve_bruteforce_batch_wide, the sets of more than
+ * MPE_MAX_DETECTIONS points). */
+int mpe_detect_batch_wide(mpe_handle* h, const uint8_t* frames, int n_frames, int rows, int cols, size_t stride_bytes,
+                          size_t frame_stride_bytes, int frames_on_device, const double K[9], const double* D, int nD,
+                          const mpe_params* p, mpe_detections_wide* dets);
+int mpe_estimate_batch_wide(mpe_handle* h, const uint8_t* frames, int n_frames, int rows, int cols, size_t stride_bytes,
+                            size_t frame_stride_bytes, int frames_on_device, const double* markers_xyz, int n_markers,
+                            const double K[9], const double* D, int nD, const mpe_params* p, mpe_result* results);
+int mpe_vote_batch_wide(mpe_handle* h, const double* det_xy, const int* n_det, int n_frames, const double* markers_xyz,
+                        int n_markers, const double K[9], double back_projection_pixel_tolerance, uint32_t* hist);
+int mpe_solve_bruteforce_batch_wide(mpe_handle* h, const double* det_xy, const int* n_det, int n,
+                                    const double* markers_xyz, int n_markers, const double K[9], const mpe_params* p,
+                                    mpe_result* out, uint32_t* hist, uint32_t* corr);
 
 /* ---- stateful estimator: the whole PoseEstimator::estimateBodyPose state machine, i.e. the
  * uninitialised branch AND the tracking path (pose_estimator.cpp:62-147): pose prediction by the

@@ -5,6 +5,7 @@ thin host-side binding used by tests / bench: ctypes over the C ABI, numpy or to
 out.  There is NO CPU fallback: if the library or a HIP device is missing every call raises.
 """
 from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYPE, DETECTIONS_DTYPE,  # noqa: F401
+                      MpeDetectionsWide, DETECTIONS_WIDE_DTYPE, WIDE_DETECTIONS,
                       MAX_DETECTIONS, MAX_MARKERS, Handle, build_library, library_path, load_library,
                       demo_params, exported_symbols, source_fingerprint, device_source, DEVICE_SOURCES, Tracker, determine_roi, distort_points, exponential_map, logarithm_map,
                       predict_pose, project_points, find_correspondences, shard_bounds, estimate_batch_multi,
@@ -15,6 +16,7 @@ from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYP
 from .pose_estimator import PoseEstimator  # noqa: F401
 
 __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE", "DETECTIONS_DTYPE",
+           "MpeDetectionsWide", "DETECTIONS_WIDE_DTYPE", "WIDE_DETECTIONS",
            "MAX_DETECTIONS", "MAX_MARKERS", "Handle", "build_library", "library_path", "load_library",
            "demo_params", "exported_symbols", "source_fingerprint", "device_source", "DEVICE_SOURCES", "PoseEstimator", "Tracker", "determine_roi", "distort_points",
            "exponential_map", "logarithm_map", "predict_pose", "project_points", "find_correspondences",

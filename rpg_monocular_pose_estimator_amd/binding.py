@@ -13,6 +13,7 @@ _HEADER = os.path.join(os.path.dirname(_HERE), "include", "mpe.h")
 
 MAX_MARKERS = 16
 MAX_DETECTIONS = int(os.environ.get("MPE_MAX_DET", "64"))  # (MPE_MAX_DET: A/B runs against a library built with another capacity)
+WIDE_DETECTIONS = 256  # MPE_WIDE_DETECTIONS: detections of one set in the *_wide entries
 
 
 class MpeError(RuntimeError):
@@ -46,12 +47,20 @@ class MpeDetections(C.Structure):
                 ("dist_xy", C.c_float * (2 * MAX_DETECTIONS))]
 
 
+class MpeDetectionsWide(C.Structure):  # mpe_detections_wide
+    _fields_ = [("n", C.c_int), ("status", C.c_int), ("undist_xy", C.c_double * (2 * WIDE_DETECTIONS)),
+                ("dist_xy", C.c_float * (2 * WIDE_DETECTIONS))]
+
+
 RESULT_DTYPE = np.dtype([("T", "f8", (16,)), ("cov", "f8", (36,)), ("status", "i4"), ("n_det", "i4"),
                          ("n_corr", "i4"), ("gn_iterations", "i4")])
 DETECTIONS_DTYPE = np.dtype([("n", "i4"), ("status", "i4"), ("undist_xy", "f8", (2 * MAX_DETECTIONS,)),
                              ("dist_xy", "f4", (2 * MAX_DETECTIONS,))])
 assert RESULT_DTYPE.itemsize == C.sizeof(MpeResult)
+DETECTIONS_WIDE_DTYPE = np.dtype([("n", "i4"), ("status", "i4"), ("undist_xy", "f8", (2 * WIDE_DETECTIONS,)),
+                                  ("dist_xy", "f4", (2 * WIDE_DETECTIONS,))])
 assert DETECTIONS_DTYPE.itemsize == C.sizeof(MpeDetections)
+assert DETECTIONS_WIDE_DTYPE.itemsize == C.sizeof(MpeDetectionsWide)
 
 
 def library_path():
@@ -98,7 +107,7 @@ def source_fingerprint():
     hsh = hashlib.sha256()
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
-                                  "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h"):
+                                  "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -174,6 +183,10 @@ def load_library():
                                      dp, dp, C.c_int, C.POINTER(MpeParams), C.c_void_p]
     lib.mpe_vote_batch.argtypes = [C.c_void_p, dp, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, C.c_double,
                                    C.POINTER(C.c_uint32)]
+    lib.mpe_vote_batch_wide.argtypes = lib.mpe_vote_batch.argtypes
+    lib.mpe_detect_batch_wide.argtypes = lib.mpe_detect_batch.argtypes
+    lib.mpe_estimate_batch_wide.argtypes = lib.mpe_estimate_batch.argtypes
+    lib.mpe_solve_bruteforce_batch_wide.argtypes = lib.mpe_solve_bruteforce_batch.argtypes
     lib.mpe_vote_items.argtypes = [C.c_void_p, dp, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, C.c_double,
                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
     lib.mpe_check_and_refine.argtypes = [C.c_void_p, dp, C.c_int, dp, C.c_int, dp, C.POINTER(MpeParams),
@@ -678,6 +691,79 @@ class Handle:
                                                   len(markers), _dp(K), C.byref(params), C.c_void_p(rec.ctypes.data),
                                                   hist.ctypes.data_as(up), corr.ctypes.data_as(up))
         self._check(rc, "mpe_solve_bruteforce_batch")
+        return rec, hist, corr
+
+    # ---- the *_wide entries: detection sets of up to WIDE_DETECTIONS points ---------------------------
+    @staticmethod
+    def _pack_dets_wide(dets):
+        n = len(dets)
+        buf = np.zeros((n, WIDE_DETECTIONS, 2))
+        nd = np.zeros(n, np.int32)
+        for i, d in enumerate(dets):
+            d = _f64(d).reshape(-1, 2)
+            nd[i] = len(d)
+            buf[i, :min(len(d), WIDE_DETECTIONS)] = d[:WIDE_DETECTIONS]  # (a longer set: the library refuses its count)
+        return buf, nd
+
+    @staticmethod
+    def _frame_args(frames):
+        if _is_torch(frames):
+            assert frames.is_cuda and frames.is_contiguous()
+            n, rows, cols = frames.shape
+            return frames, n, rows, cols, frames.data_ptr(), 1, cols, rows * cols
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, rows, cols = frames.shape
+        return frames, n, rows, cols, frames.ctypes.data, 0, frames.strides[1], frames.strides[0]
+
+    def detect_batch_wide(self, frames, K, D, params):
+        """mpe_detect_batch_wide: frames as for detect_batch.  -> records [DETECTIONS_WIDE_DTYPE] (n)."""
+        K, D = _f64(K).reshape(9), _f64(D).reshape(-1)
+        frames, n, rows, cols, ptr, on_dev, stride, fstride = self._frame_args(frames)
+        out = np.zeros(n, DETECTIONS_WIDE_DTYPE)
+        rc = self._lib.mpe_detect_batch_wide(self._h, C.c_void_p(ptr), n, rows, cols, stride, fstride, on_dev, _dp(K),
+                                             _dp(D), len(D), C.byref(params), C.c_void_p(out.ctypes.data))
+        self._check(rc, "mpe_detect_batch_wide")
+        return out
+
+    def estimate_batch_wide(self, frames, markers, K, D, params):
+        """mpe_estimate_batch_wide: estimate_batch, with the frames of 65 .. WIDE_DETECTIONS blobs solved by the wide path."""
+        markers, K, D = _f64(markers).reshape(-1, 3), _f64(K).reshape(9), _f64(D).reshape(-1)
+        frames, n, rows, cols, ptr, on_dev, stride, fstride = self._frame_args(frames)
+        out = np.zeros(n, RESULT_DTYPE)
+        rc = self._lib.mpe_estimate_batch_wide(self._h, C.c_void_p(ptr), n, rows, cols, stride, fstride, on_dev,
+                                               _dp(markers), len(markers), _dp(K), _dp(D), len(D), C.byref(params),
+                                               C.c_void_p(out.ctypes.data))
+        self._check(rc, "mpe_estimate_batch_wide")
+        return out
+
+    def vote_batch_wide(self, dets, markers, K, tol):
+        """mpe_vote_batch_wide: dets a list of (n_i, 2) arrays, n_i <= WIDE_DETECTIONS.  -> list of (n_i, n_markers)
+        uint32 histograms."""
+        markers, K = _f64(markers).reshape(-1, 3), _f64(K).reshape(9)
+        buf, nd = self._pack_dets_wide(dets)
+        n = len(nd)
+        hist = np.zeros((n, WIDE_DETECTIONS, MAX_MARKERS), np.uint32)
+        rc = self._lib.mpe_vote_batch_wide(self._h, _dp(buf), nd.ctypes.data_as(C.POINTER(C.c_int)), n, _dp(markers),
+                                           len(markers), _dp(K), float(tol), hist.ctypes.data_as(C.POINTER(C.c_uint32)))
+        self._check(rc, "mpe_vote_batch_wide")
+        return [hist[i, :nd[i], :len(markers)].copy() for i in range(n)]
+
+    def solve_bruteforce_batch_wide(self, dets, markers, K, params):
+        """mpe_solve_bruteforce_batch_wide: dets a list of (n_i, 2) arrays, n_i <= WIDE_DETECTIONS.
+        -> (records [RESULT_DTYPE] (N), histograms (N, WIDE_DETECTIONS, MAX_MARKERS) uint32, correspondences
+        (N, MAX_MARKERS, 2) uint32 — rows (marker, detection), the detection's 1-based index in its set)."""
+        markers, K = _f64(markers).reshape(-1, 3), _f64(K).reshape(9)
+        buf, nd = self._pack_dets_wide(dets)
+        n = len(nd)
+        rec = np.zeros(n, RESULT_DTYPE)
+        hist = np.zeros((n, WIDE_DETECTIONS, MAX_MARKERS), np.uint32)
+        corr = np.zeros((n, MAX_MARKERS, 2), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        rc = self._lib.mpe_solve_bruteforce_batch_wide(self._h, _dp(buf), nd.ctypes.data_as(C.POINTER(C.c_int)), n,
+                                                       _dp(markers), len(markers), _dp(K), C.byref(params),
+                                                       C.c_void_p(rec.ctypes.data), hist.ctypes.data_as(up),
+                                                       corr.ctypes.data_as(up))
+        self._check(rc, "mpe_solve_bruteforce_batch_wide")
         return rec, hist, corr
 
     def solve_bruteforce_batch_setups(self, dets, setups, item_setup):

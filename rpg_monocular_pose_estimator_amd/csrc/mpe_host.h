@@ -1,7 +1,8 @@
 // mpe_host.h — what the host-side translation units of libmpe_hip.so share (round 6: mpe_abi.cpp was one 2 800-line
 // file; it is now mpe_schedule.cpp — parameter marshalling, workspaces, the schedules of a batch (run_pipeline) —,
 // mpe_options.cpp — handle life cycle, streams, profiling read-outs, mpe_set_option / mpe_get_option —,
-// mpe_track_abi.cpp — tracked frames and lock-step time steps — and mpe_abi.cpp — every other entry of include/mpe.h;
+// mpe_track_abi.cpp — tracked frames and lock-step time steps —, mpe_wide.cpp — the *_wide entries for detection sets
+// of up to MPE_WIDE_DETECTIONS points — and mpe_abi.cpp — every other entry of include/mpe.h;
 // same exported symbols; mpe_track_device.hip holds the one kernel that is launched from here and is no part of
 // mpe_k1 / k2 / k3: the ROI gather of device-resident frames).  No torch, no CPU fallback: without a HIP device every entry point fails with
 // MPE_ERR_NO_DEVICE / MPE_ERR_HIP.
@@ -114,6 +115,10 @@ struct mpe_handle {
   // get "bruteforce_submits": device submissions of the brute-force solve entries (mpe_solve_bruteforce[_batch],
   // mpe_initialise: one each; mpe_solve_bruteforce_batch_setups: one for a fused call, one per set-up with items otherwise)
   long long bruteforce_submits = 0;
+  // the *_wide entries (mpe_wide.cpp): get "wide_frames" — detection sets mpe_solve_bruteforce_batch_wide has solved;
+  // option "wide_block_cap" (tests): blocks per set of the wide voting launch at most, 0 = four per compute unit
+  long long wide_frames = 0;
+  int wide_block_cap = 0;
   int pending_track_n = 0;            // a batch submission without its _collect yet: streams in flight
   uint8_t* pending_track_rec = nullptr;
   // How many detections the frames of a pipelined call are expected to carry: picks the voting-kernel variant (from 9

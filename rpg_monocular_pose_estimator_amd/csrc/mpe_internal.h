@@ -72,6 +72,9 @@ __host__ __device__ inline bool vote_arith_glibc_pow(int a) { return a == 3 || a
 // carries the scan paid for it (round 6: 1.54 -> 1.66 ms per launch when the table went from 2 KB to 4 KB).
 #define MPE_HIST_WORDS (MPE_MAX_DETECTIONS * MPE_MAX_MARKERS)
 #define MPE_HIST_STRIDE (MPE_HIST_WORDS + 32)
+// ... and of a detection set of the *_wide entries (up to MPE_WIDE_DETECTIONS rows): a stride constant of its own
+#define MPE_WIDE_HIST_WORDS (MPE_WIDE_DETECTIONS * MPE_MAX_MARKERS)
+#define MPE_WIDE_HIST_STRIDE (MPE_WIDE_HIST_WORDS + 32)
 
 // Hypotheses a fast voting launch does not decide itself (mpe_k2.hip, k2_sus_push): a list in device memory that
 // launch_k2_fixup works off with the strict arithmetic, behind the voting launch and in front of the tail.
@@ -180,6 +183,23 @@ hipError_t launch_k2_vote_setups(const mpe_detections* dets, const SolveParams* 
 hipError_t launch_k3_tail_setups(const mpe_detections* dets, const uint32_t* hist, int n_items, const SolveParams* setups,
                                  const int* item_setup, int max_markers, mpe_result* results, uint32_t* corr_out,
                                  void* mid_buf, hipStream_t s);
+// The *_wide entries (detection sets of up to MPE_WIDE_DETECTIONS points): the strict loop nest over a block table as
+// launch_k2_vote_setups runs it, one set-up for all items, histograms MPE_WIDE_HIST_STRIDE words apart (zeroed by the
+// caller; the votes are ADDED); vote_arith 0 / 1 / 3 / 4 (glibc's powers with 3 / 4).  Then k3_peel_wide, one wave per item:
+// all-zero test + correspondencesFromHistogram over the wide histogram; writes an ordinary record `compact` that holds
+// only the detections the rows name, the rows re-indexed into it (`corr_compact`, 2*MPE_MAX_MARKERS words per item, as
+// launch_k3_tail's corr_in reads them) and the wide index (1-based) of every slot (`slot_wide`, MPE_MAX_MARKERS per item).
+// the general blob tier alone over the frames of a device work-list (list[0] = count, then the frame indices), writing
+// wide records: kept blobs and order keys as launch_k1b_blobs' last stage computes them, the cut-off at
+// MPE_WIDE_DETECTIONS.  scratch: k1b_scratch_bytes(g, n_frames); general_lds: k1b_general_lds where the frame fits.
+hipError_t launch_k1b_general_wide(const uint8_t* frames, const unsigned long long* flags, int n_frames, const FrameGeom& g,
+                                   const DetectParams& dp, mpe_detections_wide* dets, const int* list, uint8_t* scratch,
+                                   size_t scratch_bytes, hipStream_t s, bool general_lds);
+hipError_t launch_k2_vote_wide(const mpe_detections_wide* dets, const SolveParams& sp, const BruteBlock* blocks,
+                               int n_blocks, uint32_t* hist, hipStream_t s);
+hipError_t launch_k3_peel_wide(const mpe_detections_wide* dets, const uint32_t* hist, int n_items, int n_markers,
+                               unsigned hist_thr, mpe_detections* compact, uint32_t* corr_compact, uint32_t* slot_wide,
+                               hipStream_t s);
 hipError_t launch_repack(const uint8_t* src, size_t src_stride, size_t src_frame_stride, int n_frames, int roi_x,
                          int roi_y, int roi_w, int roi_h, uint8_t* dst, int dst_pitch, hipStream_t s);
 

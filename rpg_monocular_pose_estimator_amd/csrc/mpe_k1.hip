@@ -278,8 +278,11 @@ static int k1b_gen_blocks(const FrameGeom& g, int n_frames) {
   return (int)n;
 }
 
+// (Rec / CAP: the detection record and its cut-off — mpe_detections / MPE_MAX_DETECTIONS, or mpe_detections_wide /
+//  MPE_WIDE_DETECTIONS for mpe_detect_batch_wide: the kept blobs and their order keys are the same, only the cut-off moves)
+template <class Rec = mpe_detections, int CAP = MPE_MAX_DETECTIONS>
 __global__ __launch_bounds__(64, K1B_GEN_OCC) void k1b_general(const uint8_t* __restrict__ frames, const u64* __restrict__ flags,
-                                                 FrameGeom gslot, DetectParams dp, mpe_detections* __restrict__ dets,
+                                                 FrameGeom gslot, DetectParams dp, Rec* __restrict__ dets,
                                                  const int* __restrict__ worklist, uint8_t* __restrict__ scratch,
                                                  const FrameWin* __restrict__ wins) {
   const FrameGeom& g = gslot;  // slab layout and flag indexing: the slot; rows / cols of a frame: its window (gl below)
@@ -699,7 +702,7 @@ __global__ __launch_bounds__(64, K1B_GEN_OCC) void k1b_general(const uint8_t* __
     __threadfence_block();
     __syncthreads();
     K1B_GEN_STAMP(7)
-    write_detections(kx, ky, kkey, s_nkept, K1B_GEN_KEPT, s_over, dp, dets + f, lane);
+    write_detections<Rec, CAP>(kx, ky, kkey, s_nkept, K1B_GEN_KEPT, s_over, dp, dets + f, lane);
     __syncthreads();
     K1B_GEN_STAMP(8)
 #ifdef K1B_GEN_CLOCKS
@@ -740,9 +743,10 @@ __host__ __device__ inline size_t k1b_genl_lds_bytes(const FrameGeom& g) {
 }
 static bool k1b_genl_fits(const FrameGeom& g) { return k1b_genl_lds_bytes(g) + 2048 <= (size_t)160 * 1024; }
 
+template <class Rec = mpe_detections, int CAP = MPE_MAX_DETECTIONS>
 __global__ __launch_bounds__(K1B_GENL_THREADS) void k1b_general_lds(const uint8_t* __restrict__ frames,
                                                                     const u64* __restrict__ flags, FrameGeom gslot,
-                                                                    DetectParams dp, mpe_detections* __restrict__ dets,
+                                                                    DetectParams dp, Rec* __restrict__ dets,
                                                                     const int* __restrict__ worklist,
                                                                     uint8_t* __restrict__ scratch,
                                                                     const FrameWin* __restrict__ wins) {
@@ -919,13 +923,72 @@ __global__ __launch_bounds__(K1B_GENL_THREADS) void k1b_general_lds(const uint8_
     }
     __threadfence_block();
     __syncthreads();
-    if (wv == 0) write_detections(kx, ky, kkey, s_nkept, K1B_GEN_KEPT, s_over, dp, dets + f, lane);
+    if (wv == 0) write_detections<Rec, CAP>(kx, ky, kkey, s_nkept, K1B_GEN_KEPT, s_over, dp, dets + f, lane);
     __syncthreads();
   }
 }
 
 size_t k1b_scratch_bytes(const FrameGeom& g, int n_frames) {
   return k1b_gen_scratch_bytes(g) * (size_t)k1b_gen_blocks(g, n_frames);
+}
+
+// The general tier over the frames of a device work-list (list[0] = count, then frame indices) — the last stage of
+// launch_k1b_blobs, and the whole of launch_k1b_general_wide.
+template <class Rec, int CAP>
+static hipError_t launch_k1b_general_tier(const uint8_t* frames, const unsigned long long* flags, int n_frames,
+                                          const FrameGeom& g, const DetectParams& dp, Rec* dets, const int* list,
+                                          uint8_t* scratch, size_t scratch_bytes, hipStream_t s, const FrameWin* wins,
+                                          bool general_lds) {
+  hipError_t e = hipSuccess;
+  // one slab per block: the grid follows the scratch the CALLER reserved (the process-wide knob may have moved since)
+  size_t gen_blocks = (size_t)k1b_gen_blocks(g, n_frames);
+  const size_t slabs = scratch_bytes / k1b_gen_scratch_bytes(g);
+  if (slabs < 1) return hipErrorInvalidValue;
+  if (gen_blocks > slabs) gen_blocks = slabs;
+  if (general_lds && k1b_genl_fits(g)) {
+    // frames DO reach this tier (the caller's reading of the previous call's work-list): the LDS-resident kernel, a
+    // block of four waves per CU with the frame's bitmaps in the CU's LDS
+    const size_t lds = k1b_genl_lds_bytes(g);
+    static size_t attr_set = 0;  // (the opt-in above 64 KB of dynamic LDS, once per size)
+    // (ADVICE flags this process-wide memo — the attribute belongs to a device; the wide instantiation does not repeat
+    //  it and opts in at every launch: it runs for the rare glare frame only)
+    if (lds > attr_set || CAP != MPE_MAX_DETECTIONS) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k1b_general_lds<Rec, CAP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+      if (e != hipSuccess) return e;
+      attr_set = lds;
+    }
+    const size_t cus = (size_t)device_cu_count();
+    if (gen_blocks > cus) gen_blocks = cus;
+    hipLaunchKernelGGL((k1b_general_lds<Rec, CAP>), dim3((unsigned)gen_blocks), dim3(K1B_GENL_THREADS), lds, s, frames, (const u64*)flags,
+                       g, dp, dets, list, scratch, wins);
+    return hipGetLastError();
+  }
+  // ... and no more blocks than the device holds at once: a block walks the work-list with the grid as its stride, so the
+  // blocks of a second round would start when the first round's have done ALL their frames (4 096 blocks on the 3 072
+  // resident ones of 256 CUs: the last quarter of a 16 384-frame list ran on a quarter of the machine, 7.9 ms where
+  // 5.3 rounds of frames need ~4)
+  static int resident = 0;
+  if (!resident) {
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k1b_general<Rec, CAP>), 64, 0);
+    if (e != hipSuccess) return e;
+    resident = (per_cu > 0 ? per_cu : 1) * device_cu_count();
+  }
+  static const bool full_grid = getenv("MPE_K1B_GEN_FULL_GRID") != nullptr;  // (A/B of the cap: round6_exp_general_tier.txt 8)
+  if (!full_grid && gen_blocks > (size_t)resident) gen_blocks = (size_t)resident;
+  hipLaunchKernelGGL((k1b_general<Rec, CAP>), dim3((unsigned)gen_blocks), dim3(64), 0, s, frames, (const u64*)flags, g, dp, dets,
+                     list, scratch, wins);
+  return hipGetLastError();
+}
+
+
+hipError_t launch_k1b_general_wide(const uint8_t* frames, const unsigned long long* flags, int n_frames, const FrameGeom& g,
+                                   const DetectParams& dp, mpe_detections_wide* dets, const int* list, uint8_t* scratch,
+                                   size_t scratch_bytes, hipStream_t s, bool general_lds) {
+  if (n_frames <= 0) return hipSuccess;
+  return launch_k1b_general_tier<mpe_detections_wide, MPE_WIDE_DETECTIONS>(frames, flags, n_frames, g, dp, dets, list, scratch,
+                                                                          scratch_bytes, s, nullptr, general_lds);
 }
 
 hipError_t launch_k1b_blobs(const uint8_t* frames, const unsigned long long* flags, int n_frames, const FrameGeom& g,
@@ -986,44 +1049,7 @@ hipError_t launch_k1b_blobs(const uint8_t* frames, const unsigned long long* fla
   }
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  // one slab per block: the grid follows the scratch the CALLER reserved (the process-wide knob may have moved since)
-  size_t gen_blocks = (size_t)k1b_gen_blocks(g, n_frames);
-  const size_t slabs = scratch_bytes / k1b_gen_scratch_bytes(g);
-  if (slabs < 1) return hipErrorInvalidValue;
-  if (gen_blocks > slabs) gen_blocks = slabs;
-  if (general_lds && k1b_genl_fits(g)) {
-    // frames DO reach this tier (the caller's reading of the previous call's work-list): the LDS-resident kernel, a
-    // block of four waves per CU with the frame's bitmaps in the CU's LDS
-    const size_t lds = k1b_genl_lds_bytes(g);
-    static size_t attr_set = 0;  // (the opt-in above 64 KB of dynamic LDS, once per size)
-    if (lds > attr_set) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k1b_general_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-      if (e != hipSuccess) return e;
-      attr_set = lds;
-    }
-    const size_t cus = (size_t)device_cu_count();
-    if (gen_blocks > cus) gen_blocks = cus;
-    hipLaunchKernelGGL(k1b_general_lds, dim3((unsigned)gen_blocks), dim3(K1B_GENL_THREADS), lds, s, frames, (const u64*)flags,
-                       g, dp, dets, (const int*)list_b, scratch, wins);
-    return hipGetLastError();
-  }
-  // ... and no more blocks than the device holds at once: a block walks the work-list with the grid as its stride, so the
-  // blocks of a second round would start when the first round's have done ALL their frames (4 096 blocks on the 3 072
-  // resident ones of 256 CUs: the last quarter of a 16 384-frame list ran on a quarter of the machine, 7.9 ms where
-  // 5.3 rounds of frames need ~4)
-  static int resident = 0;
-  if (!resident) {
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k1b_general), 64, 0);
-    if (e != hipSuccess) return e;
-    resident = (per_cu > 0 ? per_cu : 1) * device_cu_count();
-  }
-  static const bool full_grid = getenv("MPE_K1B_GEN_FULL_GRID") != nullptr;  // (A/B of the cap: round6_exp_general_tier.txt 8)
-  if (!full_grid && gen_blocks > (size_t)resident) gen_blocks = (size_t)resident;
-  hipLaunchKernelGGL(k1b_general, dim3((unsigned)gen_blocks), dim3(64), 0, s, frames, (const u64*)flags, g, dp, dets,
-                     (const int*)list_b, scratch, wins);
-  return hipGetLastError();
+  return launch_k1b_general_tier<mpe_detections, MPE_MAX_DETECTIONS>(frames, flags, n_frames, g, dp, dets, (const int*)list_b, scratch, scratch_bytes, s, wins, general_lds);
 }
 
 //@file-epilogue

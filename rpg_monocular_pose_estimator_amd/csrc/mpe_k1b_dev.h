@@ -1037,15 +1037,18 @@ __device__ __forceinline__ bool k1b_rows_touch(const u64* cur, const u64* prev, 
 
 // final stage: kept blobs -> OpenCV's contour order (newest first = descending raster order of
 // the start pixel), float32 centroid -> undistortPoints, write the detection record
+// (Rec / CAP: the record and its capacity — mpe_detections / MPE_MAX_DETECTIONS everywhere but in the wide instantiations
+//  of the general tier, which write mpe_detections_wide with the cut-off at MPE_WIDE_DETECTIONS)
+template <class Rec = mpe_detections, int CAP = MPE_MAX_DETECTIONS>
 __device__ __forceinline__ void write_detections(const float* kx, const float* ky, const unsigned* kkey, int nk_all,
-                                                 int kept_cap, int over, const DetectParams& dp, mpe_detections* out,
+                                                 int kept_cap, int over, const DetectParams& dp, Rec* out,
                                                  int lane) {
   const int nk = min(nk_all, kept_cap);
   for (int i = lane; i < nk; i += 64) {
     const unsigned key = kkey[i];
     int pos = 0;
     for (int j = 0; j < nk; ++j) pos += (kkey[j] > key) ? 1 : 0;
-    if (pos < MPE_MAX_DETECTIONS) {
+    if (pos < CAP) {
       const float mcx = kx[i], mcy = ky[i];
       float ux, uy;
       undistort_point(mcx, mcy, dp, ux, uy);
@@ -1056,9 +1059,9 @@ __device__ __forceinline__ void write_detections(const float* kx, const float* k
     }
   }
   if (lane == 0) {
-    out->n = min(nk_all, MPE_MAX_DETECTIONS);
+    out->n = min(nk_all, CAP);
     int st = 0;
-    if (nk_all > MPE_MAX_DETECTIONS) st = MPE_FRAME_TOO_MANY_DETECTIONS;
+    if (nk_all > CAP) st = MPE_FRAME_TOO_MANY_DETECTIONS;
     if (over) st = MPE_FRAME_TOO_MANY_ROWS;
     out->status = st;
   }

@@ -1637,6 +1637,127 @@ __global__ __launch_bounds__(K2_THREADS) void k2_vote_setups(const mpe_detection
                                 s_hist);
 }
 
+// ---- detection sets of up to MPE_WIDE_DETECTIONS points (the *_wide entries) --------------------------------------------
+// k2_strict_item for a set no 64-bit detection mask can describe: the same p3p_prepare / p3p_solution / make_projection /
+// project calls in the same statement order, every root, the triple's own votes cast here; the unused detections are
+// walked 0 .. n_d - 1 with the triple skipped — ascending, because the nearest-marker ties are broken by order
+// (pose_estimator.cpp:576-597, 862-906).  A sibling rather than a parameter of k2_strict_item, so that the narrow
+// kernels stay the instructions they were.
+template <bool GLIBC, class Vote>
+__device__ __forceinline__ void k2_strict_item_wide(const V3& fa, const V3& fb, const V3& fc, const double (*px)[2], int n_d,
+                                                    const SolveParams& sp, int c0, int c1, int c2, int p0, int p1, int p2,
+                                                    double* q, int qs, Vote vote) {
+  const int n_m = sp.n_markers, nuo = n_m - 3;
+  const V3 wa = {sp.markers[3 * p0], sp.markers[3 * p0 + 1], sp.markers[3 * p0 + 2]},
+           wb = {sp.markers[3 * p1], sp.markers[3 * p1 + 1], sp.markers[3 * p1 + 2]},
+           wc = {sp.markers[3 * p2], sp.markers[3 * p2 + 1], sp.markers[3 * p2 + 2]};
+  P3PCtx ctx;
+  if (!p3p_prepare(fa, fb, fc, wa, wb, wc, ctx, GLIBC)) return;  // computePoses returned -1
+#pragma unroll 1
+  for (int k = 0; k < 4; ++k) {
+    M3 R;
+    V3 C;
+    p3p_solution(ctx, pick_root(ctx, k), R, C);
+    if (!rc_finite(R, C)) continue;  // pose_estimator.cpp:653
+    const Proj P = make_projection(R, C, sp.fx, sp.fy, sp.cx, sp.cy);
+    int j = 0;
+    for (int m = 0; m < n_m; ++m) {  // unused markers, ascending (pose_estimator.cpp:621-661)
+      if (m == p0 || m == p1 || m == p2) continue;
+      double u, v;
+      project(P, V3{sp.markers[3 * m], sp.markers[3 * m + 1], sp.markers[3 * m + 2]}, u, v);
+      q[(2 * j) * qs] = u;
+      q[(2 * j + 1) * qs] = v;
+      ++j;
+    }
+    bool any = false;
+#pragma unroll 1
+    for (int a = 0; a < n_d; ++a) {  // unused detections, ascending
+      if (a == c0 || a == c1 || a == c2) continue;
+      double best = INFINITY;
+      int bj = 0;
+      for (int jj = 0; jj < nuo; ++jj) {
+        const double du = px[a][0] - q[(2 * jj) * qs], dv = px[a][1] - q[(2 * jj + 1) * qs];
+        const double d2 = du * du + dv * dv;
+        if (d2 < best) {
+          best = d2;
+          bj = jj;
+        }
+      }
+      if (sqrt(best) < sp.back_tol) {  // strict <, pose_estimator.cpp:671,689
+        int mi = -1, cnt = 0;
+        for (int m = 0; m < n_m; ++m) {
+          if (m == p0 || m == p1 || m == p2) continue;
+          if (cnt == bj) mi = m;
+          ++cnt;
+        }
+        vote(a, mi);
+        any = true;
+      }
+    }
+    if (any) {  // pose_estimator.cpp:676-685
+      vote(c0, p0);
+      vote(c1, p1);
+      vote(c2, p2);
+    }
+  }
+}
+
+// initialise()'s loop nest (pose_estimator.cpp:565-702) for 4 <= n_d <= MPE_WIDE_DETECTIONS: block b takes share `part` of
+// `parts` of item `item` (entry b of a BruteBlock table, mpe_brute_blocks.h) exactly as k2_vote_setups does —
+// hypotheses t = part * threads + tid, stepping parts * threads —, collects its integer votes in an LDS histogram of
+// MPE_WIDE_DETECTIONS x MPE_MAX_MARKERS words and ADDS the non-zero ones to the item's zeroed histogram
+// (MPE_WIDE_HIST_STRIDE words per item).  Static LDS: 4 KB of pixels, 6 KB of bearings, 16 KB of histogram; dynamic:
+// 2 (n_m - 3) doubles of back-projections per lane — the launcher sizes the block (256 threads up to 12 markers, 128
+// beyond) so that both stay inside the 64 KB a block has without an opt-in.  (The launch bound is that of the larger
+// block: the 128-thread launch runs the same code object, compiled for up to 256 threads.)
+template <bool GLIBC>
+__global__ __launch_bounds__(K2_THREADS) void k2_vote_wide(const mpe_detections_wide* __restrict__ dets, SolveParams sp,
+                                                           const BruteBlock* __restrict__ blocks,
+                                                           uint32_t* __restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ double s_px[MPE_WIDE_DETECTIONS][2];
+  __shared__ double s_iv[MPE_WIDE_DETECTIONS][3];
+  __shared__ unsigned s_hist[MPE_WIDE_HIST_WORDS];
+  typedef __attribute__((address_space(4))) const int* ConstInts;
+  ConstInts bb = (ConstInts)reinterpret_cast<const int*>(blocks + blockIdx.x);
+  const int item = bb[0], part = bb[1], parts = bb[2];
+  const mpe_detections_wide* d = dets + item;
+  const int n_d = d->n, n_m = sp.n_markers;
+  if (n_d < 4 || n_d > MPE_WIDE_DETECTIONS || d->status != 0 || n_m < 4) return;  // (uniform over the block)
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  for (int i = tid; i < MPE_WIDE_HIST_WORDS; i += nthr) s_hist[i] = 0;
+  for (int i = tid; i < n_d; i += nthr) {
+    const double u = d->undist_xy[2 * i], v = d->undist_xy[2 * i + 1];
+    s_px[i][0] = u;
+    s_px[i][1] = v;
+    const V3 b = bearing(u, v, sp.fx, sp.fy, sp.cx, sp.cy);
+    s_iv[i][0] = b.x;
+    s_iv[i][1] = b.y;
+    s_iv[i][2] = b.z;
+  }
+  __syncthreads();
+  double* s_q = reinterpret_cast<double*>(smem);  // back-projections: [2*j + {0,1}][tid]
+  const int n_combos = n_d * (n_d - 1) * (n_d - 2) / 6;  // (2 763 520 at 256)
+  const int n_perms = n_m * (n_m - 1) * (n_m - 2);
+  const long long total = (long long)n_combos * n_perms;  // (9.3e9 at 256 / 16)
+  for (long long t = (long long)part * nthr + tid; t < total; t += (long long)parts * nthr) {
+    const int ti = (int)(t / n_perms), pj = (int)(t - (long long)ti * n_perms);
+    int c0, c1, c2, p0, p1, p2;
+    unrank_combo3(ti, n_d, c0, c1, c2);
+    perm_from_index(pj, n_m, p0, p1, p2);
+    const V3 fa = {s_iv[c0][0], s_iv[c0][1], s_iv[c0][2]}, fb = {s_iv[c1][0], s_iv[c1][1], s_iv[c1][2]},
+             fc = {s_iv[c2][0], s_iv[c2][1], s_iv[c2][2]};
+    k2_strict_item_wide<GLIBC>(fa, fb, fc, s_px, n_d, sp, c0, c1, c2, p0, p1, p2, s_q + tid, nthr,
+                               [&](const int a, const int m) { atomicAdd(&s_hist[a * MPE_MAX_MARKERS + m], 1u); });
+  }
+  __syncthreads();
+  uint32_t* gh = hist + (size_t)item * MPE_WIDE_HIST_STRIDE;
+  for (int i = tid; i < n_d * MPE_MAX_MARKERS; i += nthr) {
+    const unsigned v = s_hist[i];
+    if (v) atomicAdd(&gh[i], v);
+  }
+}
+
 // Frames that lost a suspect entry to a full list (k2_sus_lost) are voted again, whole, with the strict loop nest: the
 // histogram is STORED over whatever the fast launch and the fix-up kernel left, the mark is cleared, the tail then
 // sees an ordinary frame.  Frames too WIDE for the fast kernels (more than MPE_FAST_VOTE_DETECTIONS detections; they
@@ -1920,6 +2041,22 @@ hipError_t launch_k2_vote_setups(const mpe_detections* dets, const SolveParams* 
   else
     hipLaunchKernelGGL(k2_vote_setups<false>, dim3((unsigned)n_blocks), dim3(threads), lds, s, dets, setups, item_setup,
                        blocks, hist);
+  return hipGetLastError();
+}
+
+hipError_t launch_k2_vote_wide(const mpe_detections_wide* dets, const SolveParams& sp, const BruteBlock* blocks,
+                               int n_blocks, uint32_t* hist, hipStream_t s) {
+  if (n_blocks <= 0 || sp.n_markers < 4) return hipSuccess;
+  if (!(vote_arith_is_strict(sp.vote_arith) || vote_arith_screens(sp.vote_arith))) return hipErrorInvalidValue;
+  // 26 KB of static LDS + 16 (n_m - 3) bytes per lane: 256 threads up to 12 markers (62 KB), 128 beyond (52 KB at 16) —
+  // inside the 64 KB a block may have without an opt-in.  The partition of an item's hypotheses among its blocks'
+  // lanes does not change what is voted: the votes are integers.
+  const int threads = sp.n_markers <= 12 ? K2_THREADS : K2_THREADS / 2;
+  const size_t lds = (size_t)(sp.n_markers - 3) * 2 * threads * sizeof(double);
+  if (vote_arith_glibc_pow(sp.vote_arith))
+    hipLaunchKernelGGL(k2_vote_wide<true>, dim3((unsigned)n_blocks), dim3(threads), lds, s, dets, sp, blocks, hist);
+  else
+    hipLaunchKernelGGL(k2_vote_wide<false>, dim3((unsigned)n_blocks), dim3(threads), lds, s, dets, sp, blocks, hist);
   return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 #include "mpe_k2_head.h"
 #include "mpe_k1b_dev.h"  // (the blob extraction's device functions: k_track_frame below runs a whole tracked frame)
 #include "mpe_pixel.h"    // (gray_px, mono16_px: the per-pixel conversion of k_to_mono8, shared with the encoded ROI gather)
+#include "mpe_wide_peel.h"  // (k3_peel_wide's logic, shared with the CPU tier)
 namespace mpe {
 //@file-prologue-end
 // =============================================================================================
@@ -1196,6 +1197,59 @@ hipError_t launch_k3_tail_setups(const mpe_detections* dets, const uint32_t* his
   const size_t lds_a = track_lds_bytes(max_markers);  // (every block lays its set-up's buffers out from the start)
   hipLaunchKernelGGL(k3_tail_setups, dim3((unsigned)n_items), dim3(64), lds_a, s, dets, hist, setups, item_setup, results,
                      corr_out, static_cast<TailMid*>(mid_buf));
+  return hipGetLastError();
+}
+
+// The tail of the *_wide entries without touching the tail kernels: checkCorrespondences and optimisePose read only the
+// detections that correspondencesFromHistogram named (pose_estimator.cpp:394-542, 733-792: image_points_ /
+// image_vectors_ are indexed through correspondences_ alone) — at most n_markers <= 16 of up to 256.  One wave per
+// item: lane c finds column c's maximum and first row in the MPE_WIDE_DETECTIONS x MPE_MAX_MARKERS histogram, lane 0
+// runs the all-zero test (pose_estimator.cpp:704) and the peeling (mpe_wide_peel.h), compacts the named detections into
+// an ordinary mpe_detections and re-indexes the rows into it; k3a_validate with given rows + the refinement kernel
+// (launch_k3_tail's corr_in, the path behind mpe_check_and_refine) finish the job.  The record is padded to 4 detections
+// with copies of its first slot when fewer distinct ones are named: k3a_body asks for 4 before it parses given rows,
+// and nothing reads a detection no row names.  An item that cannot initialise (fewer than 4 detections or markers, a
+// capacity status, an all-zero histogram) gets an empty record and no rows: status 1, identity pose.
+__global__ __launch_bounds__(64) void k3_peel_wide(const mpe_detections_wide* __restrict__ dets,
+                                                   const uint32_t* __restrict__ hist, int n_items, int n_markers,
+                                                   unsigned hist_thr, mpe_detections* __restrict__ compact,
+                                                   uint32_t* __restrict__ corr_compact, uint32_t* __restrict__ slot_wide) {
+  __shared__ unsigned s_colmax[MPE_MAX_MARKERS], s_colrow[MPE_MAX_MARKERS];
+  const int item = blockIdx.x, lane = threadIdx.x;
+  if (item >= n_items) return;
+  const mpe_detections_wide* d = dets + item;
+  const int n_d = d->n;
+  const bool can = n_d >= 4 && n_d <= MPE_WIDE_DETECTIONS && d->status == 0 && n_markers >= 4 && n_markers <= MPE_MAX_MARKERS;
+  if (can && lane < n_markers)
+    wide_column_max(hist + (size_t)item * MPE_WIDE_HIST_STRIDE, n_d, lane, s_colmax[lane], s_colrow[lane]);
+  __syncthreads();
+  if (lane != 0) return;
+  unsigned cm[MPE_MAX_MARKERS], cd[MPE_MAX_MARKERS], sw[MPE_MAX_MARKERS], cs[MPE_MAX_MARKERS];
+  const int n_c = can ? wide_peel_rows(s_colmax, s_colrow, n_markers, hist_thr, cm, cd) : 0;
+  const int n_s = wide_compact_rows(cd, n_c, sw, cs);
+  mpe_detections* o = compact + item;
+  const int n_o = n_s == 0 ? 0 : (n_s < 4 ? 4 : n_s);
+  o->n = n_o;
+  o->status = d->status;
+  for (int k = 0; k < n_o; ++k) {
+    const int w = (int)sw[k < n_s ? k : 0] - 1;
+    o->undist_xy[2 * k] = d->undist_xy[2 * w];
+    o->undist_xy[2 * k + 1] = d->undist_xy[2 * w + 1];
+    o->dist_xy[2 * k] = d->dist_xy[2 * w];
+    o->dist_xy[2 * k + 1] = d->dist_xy[2 * w + 1];
+  }
+  for (int i = 0; i < MPE_MAX_MARKERS; ++i) {
+    corr_compact[(size_t)item * 2 * MPE_MAX_MARKERS + 2 * i] = i < n_c ? cm[i] : 0u;
+    corr_compact[(size_t)item * 2 * MPE_MAX_MARKERS + 2 * i + 1] = i < n_c ? cs[i] : 0u;
+    slot_wide[(size_t)item * MPE_MAX_MARKERS + i] = sw[i];
+  }
+}
+hipError_t launch_k3_peel_wide(const mpe_detections_wide* dets, const uint32_t* hist, int n_items, int n_markers,
+                               unsigned hist_thr, mpe_detections* compact, uint32_t* corr_compact, uint32_t* slot_wide,
+                               hipStream_t s) {
+  if (n_items <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k3_peel_wide, dim3((unsigned)n_items), dim3(64), 0, s, dets, hist, n_items, n_markers, hist_thr,
+                     compact, corr_compact, slot_wide);
   return hipGetLastError();
 }
 

@@ -286,6 +286,8 @@ int mpe_get_option(mpe_handle* h, const char* name, int* value) {
   else if (n == "track_batch_chains") *value = (int)h->track_batch_chains;
   else if (n == "track_batch_reruns") *value = (int)h->track_batch_reruns;
   else if (n == "bruteforce_submits") *value = (int)h->bruteforce_submits;
+  else if (n == "wide_frames") *value = (int)h->wide_frames;
+  else if (n == "wide_block_cap") *value = h->wide_block_cap;
   else if (n == "track_ns_pack") *value = (int)(h->track_ns[0] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_enqueue") *value = (int)(h->track_ns[1] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_wait") *value = (int)(h->track_ns[2] / std::max(1LL, h->track_steps));
@@ -463,6 +465,11 @@ int mpe_set_option(mpe_handle* h, const char* name, int value) {
     h->fix_slots = 0;
     for (auto& b : h->fix_pending) b = false;
     h->fix_cap_limit = (unsigned)value;
+    return MPE_OK;
+  }
+  if (!std::strcmp(name, "wide_block_cap")) {  // tests: blocks per set of the wide voting launch at most (0 = automatic)
+    if (value < 0) return fail(h, MPE_ERR_ARG, "wide_block_cap must be >= 0");
+    h->wide_block_cap = value;
     return MPE_OK;
   }
   if (!std::strcmp(name, "vote_arith")) {

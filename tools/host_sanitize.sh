@@ -18,4 +18,11 @@ BB=$(mktemp -d)/brute_blocks_host
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
     -I rpg_monocular_pose_estimator_amd/csrc tests/host/brute_blocks_host.cpp -o $BB && $BB || rc=1
 rm -rf "$(dirname $BB)"
+# the peel-and-compact logic of k3_peel_wide (csrc/mpe_wide_peel.h) against the oracle's correspondencesFromHistogram: a
+# stand-alone program as well, the oracle's (uninstrumented) shared library linked in
+make -s -C oracle || rc=1
+WP=$(mktemp -d)/wide_peel_host
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+    -I rpg_monocular_pose_estimator_amd/csrc tests/host/wide_peel_host.cpp -o $WP -L oracle -lmpe_oracle -Wl,-rpath,$R/oracle && $WP || rc=1
+rm -rf "$(dirname $WP)"
 exit $rc
