@@ -304,49 +304,17 @@ bool PoseEstimator::estimateBodyPose(const ImageView& image, double time_to_pred
   check(handle_, mpe_tracker_set_params(tracker_, &params_), "mpe_tracker_set_params");
   check(handle_, mpe_tracker_set_camera(tracker_, camera_matrix_K_.data(), D, (int)camera_distortion_coeffs_.size()),
         "mpe_tracker_set_camera");
+  // setWideFrames: the tracker itself answers frames of 65 .. MPE_WIDE_DETECTIONS detections, in the uninitialised
+  // branch and in the tracked one (wide ROI detection, wide brute force)
+  check(handle_, mpe_tracker_set_wide_frames(tracker_, wide_frames_ ? 1 : 0), "mpe_tracker_set_wide_frames");
   if (bruteforce_every_frame_) mpe_tracker_reset(tracker_);
   predicted_time_ = time_to_predict;
   mpe_result r;
   const int rc = mpe_tracker_estimate(tracker_, image.data, image.rows, image.cols, image.step, time_to_predict, &r, 0);
-  if (rc == MPE_FRAME_TOO_MANY_DETECTIONS && wide_frames_ && (bruteforce_every_frame_ || it_since_initialized_ < 1)) {
-    // the uninitialised branch (pose_estimator.cpp:68-91) on a frame with more than 64 blobs: whole-image detection with
-    // the 256-point record, then the wide brute-force initialisation + refinement; state as optimiseAndUpdatePose leaves it
-    pullState();
-    mpe_detections_wide dw;
-    check(handle_, mpe_detect_batch_wide(handle_, image.data, 1, image.rows, image.cols, image.step,
-                                         (size_t)image.rows * image.step, 0, camera_matrix_K_.data(), D,
-                                         (int)camera_distortion_coeffs_.size(), &params_, &dw),
-          "mpe_detect_batch_wide");
-    if (dw.status < 0) throw std::runtime_error("mpe_detect_batch_wide: frame exceeded a device capacity");
-    image_points_.resize(dw.n);
-    distorted_detection_centers_.resize(dw.n);
-    for (int i = 0; i < dw.n; ++i) {
-      image_points_[i](0) = dw.undist_xy[2 * i];
-      image_points_[i](1) = dw.undist_xy[2 * i + 1];
-      distorted_detection_centers_[i].x = dw.dist_xy[2 * i];
-      distorted_detection_centers_[i].y = dw.dist_xy[2 * i + 1];
-    }
-    region_of_interest_ = Rect(0, 0, image.cols, image.rows);
-    predicted_pixel_positions_.clear();
-    pose_updated_ = false;
-    const mpe_result res = solveWide();
-    if (res.status == MPE_FRAME_POSE) {
-      for (int i = 0; i < 16; ++i) predicted_pose_(i) = res.T[i];
-      for (int i = 0; i < 36; ++i) pose_covariance_(i) = res.cov[i];
-      if (it_since_initialized_ < 2) it_since_initialized_++;
-      previous_pose_ = current_pose_;
-      current_pose_ = predicted_pose_;
-      previous_time_ = current_time_;
-      current_time_ = predicted_time_;
-      pose_updated_ = true;
-    }
-    pushState();
-    return pose_updated_;
-  }
   if (rc < 0) throw std::runtime_error(std::string("mpe_tracker_estimate: ") + mpe_last_error(handle_));
   pose_updated_ = rc == 1;
-  double xy[2 * MPE_MAX_DETECTIONS];
-  const int nd = mpe_tracker_get_image_points(tracker_, xy, MPE_MAX_DETECTIONS);
+  double xy[2 * MPE_WIDE_DETECTIONS];
+  const int nd = mpe_tracker_get_image_points(tracker_, xy, MPE_WIDE_DETECTIONS);
   image_points_.resize(nd > 0 ? nd : 0);
   for (int i = 0; i < nd; ++i) {
     image_points_[i](0) = xy[2 * i];
@@ -356,8 +324,8 @@ bool PoseEstimator::estimateBodyPose(const ImageView& image, double time_to_pred
   const int nc = mpe_tracker_get_correspondences(tracker_, corr, MPE_MAX_MARKERS);
   correspondences_.clear();
   for (int i = 0; i < nc; ++i) correspondences_.push_back({{corr[2 * i], corr[2 * i + 1]}});
-  float dxy[2 * MPE_MAX_DETECTIONS];
-  const int ndist = mpe_tracker_get_distorted_centers(tracker_, dxy, MPE_MAX_DETECTIONS);
+  float dxy[2 * MPE_WIDE_DETECTIONS];
+  const int ndist = mpe_tracker_get_distorted_centers(tracker_, dxy, MPE_WIDE_DETECTIONS);
   distorted_detection_centers_.resize(ndist > 0 ? ndist : 0);
   for (int i = 0; i < ndist; ++i) {
     distorted_detection_centers_[i].x = dxy[2 * i];

@@ -56,7 +56,9 @@ class PoseEstimator {
   //! Extension, default off: with it on, initialise() and the uninitialised branch of estimateBodyPose take the wide
   //! entries of include/mpe.h (mpe_detect_batch_wide, mpe_solve_bruteforce_batch_wide) for 65 .. MPE_WIDE_DETECTIONS
   //! detections in place of the capacity exception, and optimisePose() hands the refinement only the detections the
-  //! correspondences name.  Off, nothing changes.  The tracked branch keeps its 64-point records either way.
+  //! correspondences name.  estimateBodyPose forwards the switch to its tracker (mpe_tracker_set_wide_frames), so the
+  //! tracked branch answers glare frames too: a ROI of 65 .. 256 detections is detected with the wide record, tracked
+  //! through its nearest-neighbour rows or re-initialised by the wide brute force.  Off, nothing changes.
   void setWideFrames(bool on) { wide_frames_ = on; }
   bool getWideFrames() const { return wide_frames_; }
 

@@ -494,6 +494,27 @@ int mpe_solve_bruteforce_batch_wide(mpe_handle* h, const double* det_xy, const i
                                     const double* markers_xyz, int n_markers, const double K[9], const mpe_params* p,
                                     mpe_result* out, uint32_t* hist, uint32_t* corr);
 
+/* mpe_track_step_batch_wide ≙ mpe_track_step_batch_setups / _device / _device_encoded (the lock-step time step: ROI
+ * detection, findCorrespondences from predicted_px, checkCorrespondences, optimisePose) with records of
+ * MPE_WIDE_DETECTIONS points — a stream whose ROI fills with reflections.  Synchronous only: such steps are rare.
+ * frames_on_device 0: items[i].img are host frames (mono8: encoding must be MPE_ENC_MONO8); 1: device frames in
+ * `encoding` (MPE_ENC_*, stride_bytes in source bytes; src_big_endian for mono16).  item_setup == NULL only with
+ * n_setups == 1.  One submission: the slots are packed / gathered as the narrow entries do it, then per set-up the image
+ * scan, the general blob tier with the wide record, one small kernel (k_nn_wide: the nearest detection of every
+ * predicted pixel, first minimum wins; the detections the rows name compacted into an ordinary record) and the
+ * validation + refinement kernels; one copy back.  dets_out n records; corr_out n x 2*MPE_MAX_MARKERS words, rows
+ * (marker, detection) 1-based with detection indices 1 .. 256; out[i].status 0 = refined, 1 = fewer than 4 LEDs, no
+ * predicted_px (detection only) or rows rejected, < 0 = a capacity (more than 256 passing blobs: -10 with the first 256,
+ * as mpe_detect_batch_wide answers).  For an item with at most MPE_MAX_DETECTIONS detections every record equals the
+ * narrow entry's: n, status and the first n coordinates, the rows and n_corr, status, pose and covariance bit for bit
+ * (the tail reads only the detections the rows name, in row order).  MPE_ERR_ARG / MPE_ERR_UNSUPPORTED before any
+ * device work: the usage errors of the narrow entries, host frames with an encoding, a submission of the handle that is
+ * not yet collected.  n == 0: MPE_OK.  get "wide_track_submits" counts the submissions of this entry. */
+int mpe_track_step_batch_wide(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows, int cols,
+                              size_t stride_bytes, int frames_on_device, int encoding, int src_big_endian,
+                              const mpe_track_setup* setups, int n_setups, mpe_detections_wide* dets_out,
+                              uint32_t* corr_out, mpe_result* out);
+
 /* ---- stateful estimator: the whole PoseEstimator::estimateBodyPose state machine, i.e. the
  * uninitialised branch AND the tracking path (pose_estimator.cpp:62-147): pose prediction by the
  * constant-velocity model (predictPose :232-244), ROI from the predicted LED pixels
@@ -507,6 +528,16 @@ int mpe_tracker_set_markers(mpe_tracker* t, const double* xyz, int n); /* setMar
 int mpe_tracker_set_camera(mpe_tracker* t, const double K[9], const double* D, int nD);
 int mpe_tracker_set_params(mpe_tracker* t, const mpe_params* p);       /* tuning members / setters */
 int mpe_tracker_reset(mpe_tracker* t); /* back to "not initialised" (the reference has no reset) */
+/* on != 0: a frame on which more than MPE_MAX_DETECTIONS blobs pass the shape filter — in the ROI of a tracked stream
+ * or on the whole image of one that initialises — no longer ends with MPE_FRAME_TOO_MANY_DETECTIONS: the stream's
+ * detection is repeated with the wide record (all such streams of a time step through ONE mpe_track_step_batch_wide),
+ * and a brute force over more than MPE_MAX_DETECTIONS points goes through mpe_solve_bruteforce_batch_wide (one call per
+ * set-up; at 256 detections / 5 markers it holds the handle for about 0.43 s, and a lock-step group waits for it).
+ * The state machine is otherwise unchanged; getters and info[5] then report up to MPE_WIDE_DETECTIONS detections and
+ * correspondence indices up to 256.  What keeps the -10 code: a frame with more than MPE_WIDE_DETECTIONS passing
+ * blobs, and a wide brute force under vote_arith 2 (which has no strict form) — the other streams of the group get
+ * their records.  Honoured by every entry that drives a tracker.  Default 0: nothing changes. */
+int mpe_tracker_set_wide_frames(mpe_tracker* t, int on);
 /* estimateBodyPose(image, time_to_predict): returns 1 pose updated, 0 not, <0 error.  out (optional)
  * gets getPredictedPose / getPoseCovariance; info (optional, 8 ints) = region_of_interest_
  * x,y,w,h, it_since_initialized_, detections, correspondences, 1 if brute force ran. */

@@ -107,7 +107,8 @@ def source_fingerprint():
     hsh = hashlib.sha256()
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
-                                  "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp"):
+                                  "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
+                                  "mpe_wide_nn.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -225,6 +226,10 @@ def load_library():
     a = lib.mpe_track_step_batch_setups_device.argtypes
     lib.mpe_track_step_batch_setups_device_encoded.argtypes = a[:7] + enc + a[7:]
     lib.mpe_track_step_batch_setups_device_encoded_submit.argtypes = a[:7] + enc + a[7:9]
+    # (frames_on_device, encoding, src_big_endian) behind the stride
+    a = lib.mpe_track_step_batch_setups_device.argtypes
+    lib.mpe_track_step_batch_wide.argtypes = a[:7] + [C.c_int] + enc + a[7:]
+    lib.mpe_tracker_set_wide_frames.argtypes = [C.c_void_p, C.c_int]
     a = lib.mpe_tracker_estimate_batch.argtypes
     lib.mpe_tracker_estimate_batch_device_encoded.argtypes = a[:6] + enc + a[6:]
     a = lib.mpe_tracker_run_sequences_batch_threads.argtypes
@@ -870,7 +875,9 @@ class Handle:
             keep.append(pred)
             items[i] = TrackItem(ptrs[i], *[int(v) for v in rois[i]], None if pred is None else pred.ctypes.data)
         idx = None if item_setup is None else (C.c_int * n)(*[int(v) for v in item_setup])
-        dets, corr = np.zeros(n, DETECTIONS_DTYPE), np.zeros((n, MAX_MARKERS, 2), np.uint32)
+        wide = entry == "mpe_track_step_batch_wide"
+        dets = np.zeros(n, DETECTIONS_WIDE_DTYPE if wide else DETECTIONS_DTYPE)
+        corr = np.zeros((n, MAX_MARKERS, 2), np.uint32)
         res = np.zeros(n, RESULT_DTYPE)
         rc = getattr(self._lib, entry)(self._h, items, idx, n, rows, cols, C.c_size_t(stride), *enc, su, len(setups),
                                        C.c_void_p(dets.ctypes.data), C.c_void_p(corr.ctypes.data),
@@ -903,6 +910,28 @@ class Handle:
         else:
             out = self._track_step_batch("mpe_track_step_batch_setups_device_encoded", list(ptrs), rows, cols, stride, rois,
                                          predicted_px, setups, item_setup, _enc_args(encoding, big_endian))
+        del keep
+        return out
+
+    def track_step_batch_wide(self, imgs, rois, predicted_px, setups, item_setup=None, encoding="mono8", big_endian=False):
+        """mpe_track_step_batch_wide: track_step_batch / track_step_batch_device with records of WIDE_DETECTIONS points
+        (synchronous).  imgs: host frames as track_step_batch takes them (numpy, mono8), or device frames as
+        track_step_batch_device takes them (torch CUDA tensors, any of ENCODINGS).  -> (detections
+        [DETECTIONS_WIDE_DTYPE] (N), correspondences (N, MAX_MARKERS, 2) uint32 with detection indices 1 .. 256,
+        records [RESULT_DTYPE] (N)); for a stream of at most MAX_DETECTIONS detections, the narrow entries' records."""
+        on_device = _is_torch(imgs) or _is_torch(imgs[0])
+        if on_device:
+            keep, ptrs, (rows, cols), (stride, _) = _device_images(imgs, 0, encoding)
+            ptrs = list(ptrs)
+        else:
+            if encoding != "mono8":
+                raise MpeError("host frames are mono8 (the encodings are decoded from device frames)")
+            rows, cols = imgs[0].shape
+            stride = imgs[0].strides[0]
+            assert all(im.dtype == np.uint8 and im.shape == (rows, cols) and im.strides == (stride, 1) for im in imgs)
+            keep, ptrs = imgs, [im.ctypes.data for im in imgs]
+        out = self._track_step_batch("mpe_track_step_batch_wide", ptrs, rows, cols, stride, rois, predicted_px, setups,
+                                     item_setup, (int(on_device),) + _enc_args(encoding, big_endian))
         del keep
         return out
 
@@ -1087,6 +1116,10 @@ class Tracker:
 
     def reset(self):
         self._lib.mpe_tracker_reset(self._t)
+
+    def set_wide_frames(self, on):
+        """mpe_tracker_set_wide_frames: frames of 65 .. WIDE_DETECTIONS detections are answered (default off)."""
+        self._handle._check(self._lib.mpe_tracker_set_wide_frames(self._t, int(bool(on))), "mpe_tracker_set_wide_frames")
 
     def estimate(self, img, time):
         img = np.ascontiguousarray(img, np.uint8)

@@ -98,6 +98,7 @@ struct mpe_handle {
     const uint8_t* d_pix = nullptr;
     const void* d_wins = nullptr;
     const double* d_pred = nullptr;
+    const int* d_list = nullptr;  // wide submissions: one identity work-list per range, range r's at d_list + begin + r
     struct Range {
       int begin = 0, count = 0;
       bool optimistic = false;  // 1 .. 8 markers: the small blob tier alone, the whole chain again in _collect if need be
@@ -118,6 +119,7 @@ struct mpe_handle {
   // the *_wide entries (mpe_wide.cpp): get "wide_frames" — detection sets mpe_solve_bruteforce_batch_wide has solved;
   // option "wide_block_cap" (tests): blocks per set of the wide voting launch at most, 0 = four per compute unit
   long long wide_frames = 0;
+  long long wide_track_submits = 0;  // get "wide_track_submits": submissions of mpe_track_step_batch_wide
   int wide_block_cap = 0;
   int pending_track_n = 0;            // a batch submission without its _collect yet: streams in flight
   uint8_t* pending_track_rec = nullptr;

@@ -192,9 +192,15 @@ hipError_t launch_k3_tail_setups(const mpe_detections* dets, const uint32_t* his
 // the general blob tier alone over the frames of a device work-list (list[0] = count, then the frame indices), writing
 // wide records: kept blobs and order keys as launch_k1b_blobs' last stage computes them, the cut-off at
 // MPE_WIDE_DETECTIONS.  scratch: k1b_scratch_bytes(g, n_frames); general_lds: k1b_general_lds where the frame fits.
+// frame_windows: as launch_k1b_blobs' (the ROI slots of mpe_track_step_batch_wide), or nullptr for whole frames.
 hipError_t launch_k1b_general_wide(const uint8_t* frames, const unsigned long long* flags, int n_frames, const FrameGeom& g,
                                    const DetectParams& dp, mpe_detections_wide* dets, const int* list, uint8_t* scratch,
-                                   size_t scratch_bytes, hipStream_t s, bool general_lds);
+                                   size_t scratch_bytes, hipStream_t s, bool general_lds,
+                                   const void* frame_windows = nullptr);
+// k_nn_wide, one wave per item: findCorrespondences (mpe_wide_nn.h) from `pred` (2 * MPE_MAX_MARKERS doubles per item)
+// over a wide record, then k3_peel_wide's hand-over (compact / corr_compact / slot_wide as below)
+hipError_t launch_k_nn_wide(const mpe_detections_wide* dets, const double* pred, int n_items, int n_markers, double nn_tol,
+                            mpe_detections* compact, uint32_t* corr_compact, uint32_t* slot_wide, hipStream_t s);
 hipError_t launch_k2_vote_wide(const mpe_detections_wide* dets, const SolveParams& sp, const BruteBlock* blocks,
                                int n_blocks, uint32_t* hist, hipStream_t s);
 hipError_t launch_k3_peel_wide(const mpe_detections_wide* dets, const uint32_t* hist, int n_items, int n_markers,

@@ -985,10 +985,12 @@ static hipError_t launch_k1b_general_tier(const uint8_t* frames, const unsigned 
 
 hipError_t launch_k1b_general_wide(const uint8_t* frames, const unsigned long long* flags, int n_frames, const FrameGeom& g,
                                    const DetectParams& dp, mpe_detections_wide* dets, const int* list, uint8_t* scratch,
-                                   size_t scratch_bytes, hipStream_t s, bool general_lds) {
+                                   size_t scratch_bytes, hipStream_t s, bool general_lds, const void* frame_windows) {
   if (n_frames <= 0) return hipSuccess;
   return launch_k1b_general_tier<mpe_detections_wide, MPE_WIDE_DETECTIONS>(frames, flags, n_frames, g, dp, dets, list, scratch,
-                                                                          scratch_bytes, s, nullptr, general_lds);
+                                                                          scratch_bytes, s,
+                                                                          static_cast<const FrameWin*>(frame_windows),
+                                                                          general_lds);
 }
 
 hipError_t launch_k1b_blobs(const uint8_t* frames, const unsigned long long* flags, int n_frames, const FrameGeom& g,

@@ -5,6 +5,7 @@
 #include "mpe_k1b_dev.h"  // (the blob extraction's device functions: k_track_frame below runs a whole tracked frame)
 #include "mpe_pixel.h"    // (gray_px, mono16_px: the per-pixel conversion of k_to_mono8, shared with the encoded ROI gather)
 #include "mpe_wide_peel.h"  // (k3_peel_wide's logic, shared with the CPU tier)
+#include "mpe_wide_nn.h"    // (k_nn_wide's, likewise)
 namespace mpe {
 //@file-prologue-end
 // =============================================================================================
@@ -1250,6 +1251,66 @@ hipError_t launch_k3_peel_wide(const mpe_detections_wide* dets, const uint32_t* 
   if (n_items <= 0) return hipSuccess;
   hipLaunchKernelGGL(k3_peel_wide, dim3((unsigned)n_items), dim3(64), 0, s, dets, hist, n_items, n_markers, hist_thr,
                      compact, corr_compact, slot_wide);
+  return hipGetLastError();
+}
+
+// The tracked path over a wide record (mpe_track_step_batch_wide): findCorrespondences from the item's predicted marker
+// pixels (mpe_wide_nn.h), one wave per item — lane l keeps detections l, l + 64, l + 128, l + 192 in registers (no LDS
+// for them), every marker is one pass over the lane's four and a butterfly reduction of the pairs (d2, index) — then
+// lane 0 makes k3_peel_wide's hand-over: the compact record, the rows re-indexed into it, the slot -> wide index table.
+// An item that cannot go on (fewer than 4 detections or markers, a capacity status, NaN predictions = detection only,
+// no row kept) gets the empty record and no rows: the tail reports status 1 (or the capacity code).
+__global__ __launch_bounds__(64) void k_nn_wide(const mpe_detections_wide* __restrict__ dets,
+                                                const double* __restrict__ pred, int n_items, int n_markers,
+                                                double nn_tol, mpe_detections* __restrict__ compact,
+                                                uint32_t* __restrict__ corr_compact, uint32_t* __restrict__ slot_wide) {
+  __shared__ unsigned s_cm[MPE_MAX_MARKERS], s_cd[MPE_MAX_MARKERS];
+  const int item = blockIdx.x, lane = threadIdx.x;
+  if (item >= n_items) return;
+  const mpe_detections_wide* d = dets + item;
+  const int n_d = d->n;
+  const bool can = n_d >= 4 && n_d <= MPE_WIDE_DETECTIONS && d->status == 0 && n_markers >= 4 && n_markers <= MPE_MAX_MARKERS;
+  double lx[MPE_WIDE_NN_PER_LANE], ly[MPE_WIDE_NN_PER_LANE];
+#pragma unroll
+  for (int k = 0; k < MPE_WIDE_NN_PER_LANE; ++k) {
+    const int j = lane + 64 * k;
+    const bool in = can && j < n_d;
+    lx[k] = in ? d->undist_xy[2 * j] : 0.0;
+    ly[k] = in ? d->undist_xy[2 * j + 1] : 0.0;
+  }
+  int n_c = 0;  // (wave-uniform: every lane holds the reduction's result)
+  const double* pp = pred + (size_t)item * 2 * MPE_MAX_MARKERS;
+  for (int i = 0; can && i < n_markers; ++i) {
+    double best;
+    unsigned bj;
+    wide_nn_lane(lx, ly, lane, n_d, pp[2 * i], pp[2 * i + 1], best, bj);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+      const double ob = __shfl_xor(best, m, 64);
+      const unsigned oj = (unsigned)__shfl_xor((int)bj, m, 64);
+      if (wide_nn_better(ob, oj, best, bj)) {
+        best = ob;
+        bj = oj;
+      }
+    }
+    if (wide_nn_keep(best, bj, nn_tol)) {
+      if (lane == 0) {
+        s_cm[n_c] = (unsigned)i + 1u;
+        s_cd[n_c] = bj;
+      }
+      ++n_c;
+    }
+  }
+  __syncthreads();
+  if (lane != 0) return;
+  wide_hand_over(d, s_cm, s_cd, n_c, compact + item, corr_compact + (size_t)item * 2 * MPE_MAX_MARKERS,
+                 slot_wide + (size_t)item * MPE_MAX_MARKERS);
+}
+hipError_t launch_k_nn_wide(const mpe_detections_wide* dets, const double* pred, int n_items, int n_markers, double nn_tol,
+                            mpe_detections* compact, uint32_t* corr_compact, uint32_t* slot_wide, hipStream_t s) {
+  if (n_items <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nn_wide, dim3((unsigned)n_items), dim3(64), 0, s, dets, pred, n_items, n_markers, nn_tol, compact,
+                     corr_compact, slot_wide);
   return hipGetLastError();
 }
 

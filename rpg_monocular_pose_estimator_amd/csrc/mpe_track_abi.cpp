@@ -27,6 +27,23 @@ struct TrackRecords {
   }
 };
 
+// ... and of a wide submission (mpe_track_step_batch_wide): n wide detection sets, n x 2*MPE_MAX_MARKERS correspondence
+// words (indices into the compact record the tail ran on), n x MPE_MAX_MARKERS slot -> wide index words, n results
+struct WideTrackRecords {
+  mpe_detections_wide* dets;
+  uint32_t* corr;
+  uint32_t* slot;
+  mpe_result* res;
+  WideTrackRecords(void* base, int n)
+      : dets(static_cast<mpe_detections_wide*>(base)),
+        corr(reinterpret_cast<uint32_t*>(dets + n)),
+        slot(corr + (size_t)n * 2 * MPE_MAX_MARKERS),
+        res(reinterpret_cast<mpe_result*>(slot + (size_t)n * MPE_MAX_MARKERS)) {}
+  static size_t bytes(int n) {
+    return (size_t)n * (sizeof(mpe_detections_wide) + 3 * MPE_MAX_MARKERS * sizeof(uint32_t) + sizeof(mpe_result));
+  }
+};
+
 bool roi_inside(const mpe_track_item& it, int rows, int cols) {
   return it.roi_x >= 0 && it.roi_y >= 0 && it.roi_w > 0 && it.roi_h > 0 && it.roi_x + it.roi_w <= cols &&
          it.roi_y + it.roi_h <= rows;
@@ -146,11 +163,14 @@ int track_range_chain(mpe_handle* h, const mpe_handle::PendingTrack::Range& r, i
 // in source bytes, the ROIs in pixels) k_gather_rois_encoded writes them, decoding what it gathers — the slots are mono8
 // whatever the source was, so nothing behind the gather, the overflow re-run in _collect included, knows the encoding.
 // The caller has checked the arguments and entered the handle.
+// wide (mpe_track_step_batch_wide): the same slots, header and gather, nothing launched behind them — no range is fused,
+// the header also carries one identity work-list per range for the general blob tier, the record area is sized for
+// WideTrackRecords, and the submission is not left pending: run_wide_slots works it off synchronously.
 enum PixelSource { kHostFrames, kDeviceFrames, kEncodedDeviceFrames };
 
 int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, const FrameGeom& g,
                  size_t stride_bytes, const TrackSetup* setups, int n_setups, PixelSource source = kHostFrames,
-                 size_t img_bytes = 0, int encoding = MPE_ENC_MONO8, int big_endian = 0) {
+                 size_t img_bytes = 0, int encoding = MPE_ENC_MONO8, int big_endian = 0, bool wide = false) {
   const bool on_device = source != kHostFrames;
   mpe_handle::PendingTrack& pt = h->pending_track;
   pt.t_in = h->track_profile ? clk::now() : clk::time_point();
@@ -165,7 +185,7 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
       if (!count[(size_t)s] || opt != (pass == 0)) continue;
       const int begin = pt.ranges.empty() ? 0 : pt.ranges.back().begin + pt.ranges.back().count;
       range_of[(size_t)s] = (int)pt.ranges.size();
-      pt.ranges.push_back({begin, count[(size_t)s], opt, opt && h->track_fused != 0, setups[s]});
+      pt.ranges.push_back({begin, count[(size_t)s], opt, opt && h->track_fused != 0 && !wide, setups[s]});
       if (pt.ranges.back().fused) {
         n_fused += count[(size_t)s];
         ++fused_setups;
@@ -187,11 +207,13 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   const size_t win_bytes = ((size_t)n * 4 * sizeof(int) + 15) & ~(size_t)15;
   const size_t tab_bytes = table ? (pt.ranges.size() * sizeof(TrackSetup) + 255) & ~(size_t)255 : 0;
   const size_t idx_bytes = table ? ((size_t)n * sizeof(int) + 15) & ~(size_t)15 : 0;
-  const size_t gat_off = pred_bytes + win_bytes + tab_bytes + idx_bytes;
+  const size_t list_off = pred_bytes + win_bytes + tab_bytes + idx_bytes;
+  const size_t list_bytes = wide ? (((size_t)n + pt.ranges.size()) * sizeof(int) + 15) & ~(size_t)15 : 0;
+  const size_t gat_off = list_off + list_bytes;
   const size_t head_bytes = gat_off + (on_device ? (size_t)n * sizeof(GatherItem) : 0);  // (a multiple of 16: the slots' alignment)
   const size_t in_bytes = head_bytes + (size_t)n * slot;
   const size_t staged_bytes = on_device ? head_bytes : in_bytes;
-  const size_t rec_bytes = TrackRecords::bytes(n);
+  const size_t rec_bytes = wide ? WideTrackRecords::bytes(n) : TrackRecords::bytes(n);
   int rc = grow_mailbox(h, staged_bytes + rec_bytes + 512);
   if (rc != MPE_OK) return rc;
   uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
@@ -204,6 +226,13 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     for (size_t r = 0; r < pt.ranges.size(); ++r) {
       tab[r] = pt.ranges[r].su;
       for (int k = pt.ranges[r].begin; k < pt.ranges[r].begin + pt.ranges[r].count; ++k) slot_setup[k] = (int)r;
+    }
+  }
+  if (wide) {  // range r's list: its count, then its slots relative to its first one
+    int* list = reinterpret_cast<int*>(mb + list_off);
+    for (const mpe_handle::PendingTrack::Range& r : pt.ranges) {
+      *list++ = r.count;
+      for (int k = 0; k < r.count; ++k) *list++ = k;
     }
   }
   const double qnan = std::nan("");
@@ -225,6 +254,11 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   }
   uint8_t* host_rec = mb + ((staged_bytes + 255) & ~(size_t)255);
   if ((rc = reserve_track(h, g, n, in_bytes)) != MPE_OK) return rc;
+  if (wide) {  // (the compact records and rows k_nn_wide hands to the tail stay on the device)
+    HIP_TRY(h, h->track.reserve(rec_bytes));
+    HIP_TRY(h, h->dets.reserve((size_t)n * sizeof(mpe_detections)));
+    HIP_TRY(h, h->corr.reserve((size_t)n * 2 * MPE_MAX_MARKERS * sizeof(uint32_t)));
+  }
   uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
   h->have_ms = false;
   if (h->track_profile) pt.t_packed = clk::now();
@@ -238,12 +272,17 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   pt.d_pred = reinterpret_cast<const double*>(d_in);
   pt.d_wins = d_in + pred_bytes;
   pt.d_pix = d_in + head_bytes;
+  pt.d_list = reinterpret_cast<const int*>(d_in + list_off);
   if (source == kDeviceFrames)
     HIP_TRY(h, launch_gather_rois(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g, stride_bytes,
                                   img_bytes, h->stream));
   else if (source == kEncodedDeviceFrames)
     HIP_TRY(h, launch_gather_rois_encoded(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g,
                                           stride_bytes, img_bytes, encoding, big_endian, h->stream));
+  if (wide) {
+    h->pending_track_rec = host_rec;  // (for run_wide_slots, which follows at once: nothing stays pending)
+    return MPE_OK;
+  }
   ++h->track_batch_submits;
   // round 6: the fused ranges as ONE launch, a block per stream (k_track_frame), the records stored to the pinned
   // staging memory by the kernel (track_fused 2) — scan, small blob tier, tail and copy-out were five commands, and
@@ -415,6 +454,83 @@ int mpe_track_step_batch_setups(mpe_handle* h, const mpe_track_item* items, cons
   if (rc != MPE_OK) return rc;
   if (n == 0) return MPE_OK;  // (nothing was submitted)
   return mpe_track_step_batch_collect(h, dets_out, corr_out, out);
+}
+
+namespace {
+// The wide submission submit_slots has staged (wide = true), worked off: per set-up range the image scan, the general
+// blob tier with the wide writer and the slot windows, k_nn_wide (correspondences from the predicted pixels, compact
+// record + rows) and the tail with given rows; one copy back, rows mapped back to wide indices, items un-permuted.
+static int run_wide_slots(mpe_handle* h, int n, mpe_detections_wide* dets_out, uint32_t* corr_out, mpe_result* out) {
+  const mpe_handle::PendingTrack& pt = h->pending_track;
+  uint8_t* host_rec = h->pending_track_rec;
+  h->pending_track_rec = nullptr;
+  const WideTrackRecords d(h->track.p, n), rec(host_rec, n);
+  unsigned long long* flags = static_cast<unsigned long long*>(h->flags.p);
+  mpe_detections* compact = static_cast<mpe_detections*>(h->dets.p);
+  uint32_t* rows_in = static_cast<uint32_t*>(h->corr.p);
+  ++h->wide_track_submits;
+  size_t ri = 0;
+  for (const mpe_handle::PendingTrack::Range& r : pt.ranges) {
+    const uint8_t* pix = pt.d_pix + (size_t)r.begin * pt.slot_bytes;
+    const int* wins = static_cast<const int*>(pt.d_wins) + 4 * (size_t)r.begin;
+    const size_t c0 = (size_t)r.begin * 2 * MPE_MAX_MARKERS;
+    HIP_TRY(h, launch_k1a_scan(pix, (size_t)r.count * pt.slot_bytes, flags, r.su.dp.thr, 0, h->stream));
+    HIP_TRY(h, launch_k1b_general_wide(pix, flags, r.count, pt.g, r.su.dp, d.dets + r.begin, pt.d_list + r.begin + ri,
+                                       static_cast<uint8_t*>(h->scratch.p), h->scratch.cap, h->stream, h->general_lds == 1,
+                                       wins));
+    HIP_TRY(h, launch_k_nn_wide(d.dets + r.begin, pt.d_pred + c0, r.count, r.su.sp.n_markers, r.su.nn_tol,
+                                compact + r.begin, rows_in + c0, d.slot + (size_t)r.begin * MPE_MAX_MARKERS, h->stream));
+    // (the validation kernel takes its rows from rows_in and never reads a histogram: the pointer is only offset)
+    HIP_TRY(h, launch_k3_tail(compact + r.begin, static_cast<uint32_t*>(h->hist.p), r.count, r.su.sp, d.res + r.begin,
+                              d.corr + c0, rows_in + c0, nullptr, 0.0, h->mid.p, h->stream, 0));
+    ++ri;
+  }
+  HIP_TRY(h, hipMemcpyAsync(host_rec, h->track.p, pt.rec_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int k = 0; k < n; ++k) {  // slot k -> the caller's item perm[k]
+    const int i = pt.perm[(size_t)k];
+    dets_out[i] = rec.dets[k];
+    out[i] = rec.res[k];
+    out[i].n_det = rec.dets[k].n;
+    uint32_t* co = corr_out + (size_t)i * 2 * MPE_MAX_MARKERS;
+    const uint32_t* ci = rec.corr + (size_t)k * 2 * MPE_MAX_MARKERS;
+    std::memset(co, 0, 2 * MPE_MAX_MARKERS * sizeof(uint32_t));
+    for (int r = 0; r < out[i].n_corr && r < MPE_MAX_MARKERS; ++r) {
+      const uint32_t s = ci[2 * r + 1];
+      co[2 * r] = ci[2 * r];
+      co[2 * r + 1] = (s >= 1 && s <= MPE_MAX_MARKERS) ? rec.slot[(size_t)k * MPE_MAX_MARKERS + (s - 1)] : 0u;
+    }
+  }
+  return MPE_OK;
+}
+}  // namespace
+
+int mpe_track_step_batch_wide(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows, int cols,
+                              size_t stride_bytes, int frames_on_device, int encoding, int src_big_endian,
+                              const mpe_track_setup* setups, int n_setups, mpe_detections_wide* dets_out,
+                              uint32_t* corr_out, mpe_result* out) {
+  // every usage error before any device work: those of the narrow entries of the same source
+  if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || rows < 1 || cols < 1 ||
+      !dets_out || !corr_out || !out)
+    return fail(h, MPE_ERR_ARG, "bad argument");
+  const size_t bpp = (size_t)encoding_bytes_per_pixel(encoding);
+  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+  if (!frames_on_device && encoding != MPE_ENC_MONO8)
+    return fail(h, MPE_ERR_ARG, "host frames are mono8 (the encodings are decoded from device frames)");
+  if (stride_bytes < (size_t)cols * bpp) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (h->submit_seq != h->collect_seq) return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+  FrameGeom g;
+  std::vector<TrackSetup> prep;
+  int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
+  if (rc != MPE_OK || n == 0) return rc;
+  ENTER(h);
+  const PixelSource source = !frames_on_device ? kHostFrames : encoding == MPE_ENC_MONO8 ? kDeviceFrames : kEncodedDeviceFrames;
+  const size_t img_bytes = (size_t)(rows - 1) * stride_bytes + (size_t)cols * bpp;
+  if (frames_on_device && (rc = check_device_images(h, items, n, img_bytes)) != MPE_OK) return rc;
+  if ((rc = submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups, source, img_bytes, encoding,
+                         src_big_endian ? 1 : 0, true)) != MPE_OK)
+    return rc;
+  return run_wide_slots(h, n, dets_out, corr_out, out);
 }
 
 int mpe_track_step_batch_cancel(mpe_handle* h) {

@@ -3,7 +3,9 @@
 // runs in the kernels through the public C ABI.  One state machine (BatchCtx) serves one stream and
 // N streams in lock step alike: its device steps are the lock-step submissions
 // (mpe_track_step_batch_setups_submit / _collect: detection in the ROI with correspondences,
-// validation and refinement) and mpe_solve_bruteforce_batch (re-initialisation).
+// validation and refinement) and mpe_solve_bruteforce_batch (re-initialisation); with
+// mpe_tracker_set_wide_frames, frames of 65 .. MPE_WIDE_DETECTIONS detections repeat those two steps
+// through mpe_track_step_batch_wide and mpe_solve_bruteforce_batch_wide.
 //
 // Reference: PoseEstimator::estimateBodyPose (pose_estimator.cpp:62-147), predictPose (:232-244),
 // predictMarkerPositionsInImage (:270-276), findCorrespondences (:372-392), updatePose /
@@ -220,6 +222,7 @@ struct mpe_tracker {
   std::vector<uint32_t> corr;        // rows (marker, detection)
   int n_corr = 0, gn_iterations = 0;
   bool used_bruteforce = false;
+  bool wide_frames = false;  // mpe_tracker_set_wide_frames
   BatchCtx* solo = nullptr;  // mpe_tracker_estimate's lock-step group of one, kept for its buffers
   ~mpe_tracker();
 };
@@ -425,6 +428,12 @@ int mpe_tracker_set_params(mpe_tracker* t, const mpe_params* p) {
   return MPE_OK;
 }
 
+int mpe_tracker_set_wide_frames(mpe_tracker* t, int on) {
+  if (!t) return MPE_ERR_ARG;
+  t->wide_frames = on != 0;
+  return MPE_OK;
+}
+
 int mpe_tracker_reset(mpe_tracker* t) {
   if (!t) return MPE_ERR_ARG;
   t->it_since_initialized = 0;
@@ -465,7 +474,9 @@ int mpe_tracker_get_distorted_centers(mpe_tracker* t, float* xy, int cap_points)
 }  // extern "C"
 
 namespace {
-enum BatchOp { OP_DETECT, OP_BRUTE, OP_DONE };
+// (OP_DETECT_WIDE: the stream's detection said MPE_FRAME_TOO_MANY_DETECTIONS and its tracker has the wide switch on —
+//  the same detection again through mpe_track_step_batch_wide)
+enum BatchOp { OP_DETECT, OP_BRUTE, OP_DONE, OP_DETECT_WIDE };
 struct BatchLane {
   BatchOp op = OP_DONE;
   bool tracking = false;  // false: uninitialised branch (detection only, then brute force)
@@ -492,6 +503,7 @@ struct BatchCtx {
   std::vector<mpe_detections> dets;
   std::vector<uint32_t> corr;
   std::vector<mpe_result> res;
+  std::vector<mpe_detections_wide> wdets;  // records of a wide DETECT call
   // the lanes' set-ups — camera, markers, parameters — as mpe_track_setup entries pointing into the first tracker of
   // each set-up (a uniform group has one), and the set-up of every lane.  mixed (the *_mixed entries) admits lanes of
   // different set-ups on one handle; otherwise every lane must have the first one's.
@@ -568,12 +580,13 @@ struct BatchCtx {
 
   // submit the DETECT lanes of one size class (two classes, so that a few whole-image retries do not inflate every
   // ROI slot of the batch); returns the number of lanes submitted or < 0
-  int submit_detect(int big) {
+  // the lanes at `op` (of size class `big`; < 0: both) as items of a lock-step submission; pend = those lanes
+  void gather_items(BatchOp op, int big) {
     items.clear();
     item_setup.clear();
     pend.clear();
     for (int i = 0; i < n; ++i) {
-      if (L[(size_t)i].op != OP_DETECT || (int)is_big(i) != big) continue;
+      if (L[(size_t)i].op != op || (big >= 0 && (int)is_big(i) != big)) continue;
       const mpe_tracker* t = ts[i];
       mpe_track_item it;
       it.img = imgs[i];
@@ -586,6 +599,9 @@ struct BatchCtx {
       item_setup.push_back(lane_setup[(size_t)i]);
       pend.push_back(i);
     }
+  }
+  int submit_detect(int big) {
+    gather_items(OP_DETECT, big);
     if (items.empty()) return 0;
     // (MPE_ENC_MONO8: the encoded entry hands the call to mpe_track_step_batch_setups_device_submit)
     const int rc = frames_on_device
@@ -611,50 +627,146 @@ struct BatchCtx {
     const int rc = mpe_track_step_batch_collect(h, dets.data(), corr.data(), res.data());
     if (rc != MPE_OK) return rc;
     for (int k = 0; k < m; ++k) {
-      const int i = pend[(size_t)k];
-      mpe_tracker* t = ts[i];
-      BatchLane& ln = L[(size_t)i];
       const mpe_detections& d = dets[(size_t)k];
-      if (d.status != 0) {  // device capacity exceeded on this stream's frame
-        ln.error = d.status;
-        ln.op = OP_DONE;
-        continue;
-      }
-      t->det_dist.assign(d.dist_xy, d.dist_xy + 2 * d.n);
-      if (d.n > 0) t->det.assign(d.undist_xy, d.undist_xy + 2 * d.n);  // kept when nothing was found
-      if (!ln.tracking) {  // pose_estimator.cpp:80-91
-        ln.op = (t->det.size() / 2 >= 4) ? OP_BRUTE : OP_DONE;
-        continue;
-      }
-      ln.num_loops++;  // pose_estimator.cpp:105-144
-      if (t->det.size() / 2 >= 4) {
-        // (>= 4 detections can only come from this very detection: the device already ran findCorrespondences +
-        //  checkCorrespondences + optimisePose on them)
-        const mpe_result& r = res[(size_t)k];
-        if (r.status < 0) {
-          ln.error = r.status;
-          ln.op = OP_DONE;
-          continue;
-        }
-        t->n_corr = r.n_corr;
-        t->corr.assign(corr.begin() + (size_t)k * 2 * MPE_MAX_MARKERS,
-                       corr.begin() + (size_t)k * 2 * MPE_MAX_MARKERS + 2 * r.n_corr);
-        if (r.status == MPE_FRAME_POSE) {
-          take_result(t, r);
-          ln.op = OP_DONE;
-        } else {
-          ln.op = OP_BRUTE;  // reinitialise if the correspondences were not valid
-        }
-      } else if (ln.num_loops < 2) {  // too few LEDs in the ROI: search the whole image once
-        t->roi[0] = t->roi[1] = 0;
-        t->roi[2] = cols;
-        t->roi[3] = rows;
-        ln.op = OP_DETECT;
-      } else {
-        ln.op = OP_DONE;
-      }
+      advance(pend[(size_t)k], d.n, d.status, d.undist_xy, d.dist_xy, res[(size_t)k], &corr[(size_t)k * 2 * MPE_MAX_MARKERS],
+              false);
     }
     pend.clear();
+    return MPE_OK;
+  }
+
+  // lane i behind its detection record (narrow or wide: n_det points, status) with the result and rows the device
+  // made from it
+  void advance(int i, int n_det, int status, const double* undist_xy, const float* dist_xy, const mpe_result& r,
+               const uint32_t* rows_md, bool from_wide) {
+    mpe_tracker* t = ts[i];
+    BatchLane& ln = L[(size_t)i];
+    const bool go_wide = t->wide_frames && !from_wide;
+    if (status != 0) {  // device capacity exceeded on this stream's frame
+      if (go_wide && status == MPE_FRAME_TOO_MANY_DETECTIONS) {
+        ln.op = OP_DETECT_WIDE;
+        return;
+      }
+      ln.error = status;
+      ln.op = OP_DONE;
+      return;
+    }
+    if (go_wide && r.status == MPE_FRAME_TOO_MANY_DETECTIONS) {  // (the code on the result alone)
+      ln.op = OP_DETECT_WIDE;
+      return;
+    }
+    t->det_dist.assign(dist_xy, dist_xy + 2 * n_det);
+    if (n_det > 0) t->det.assign(undist_xy, undist_xy + 2 * n_det);  // kept when nothing was found
+    if (!ln.tracking) {  // pose_estimator.cpp:80-91
+      ln.op = (t->det.size() / 2 >= 4) ? OP_BRUTE : OP_DONE;
+      return;
+    }
+    ln.num_loops++;  // pose_estimator.cpp:105-144
+    if (t->det.size() / 2 >= 4) {
+      // (>= 4 detections can only come from this very detection: the device already ran findCorrespondences +
+      //  checkCorrespondences + optimisePose on them)
+      if (r.status < 0) {
+        ln.error = r.status;
+        ln.op = OP_DONE;
+        return;
+      }
+      t->n_corr = r.n_corr;
+      t->corr.assign(rows_md, rows_md + 2 * r.n_corr);
+      if (r.status == MPE_FRAME_POSE) {
+        take_result(t, r);
+        ln.op = OP_DONE;
+      } else {
+        ln.op = OP_BRUTE;  // reinitialise if the correspondences were not valid
+      }
+    } else if (ln.num_loops < 2) {  // too few LEDs in the ROI: search the whole image once
+      t->roi[0] = t->roi[1] = 0;
+      t->roi[2] = cols;
+      t->roi[3] = rows;
+      ln.op = OP_DETECT;
+    } else {
+      ln.op = OP_DONE;
+    }
+  }
+
+  // all OP_DETECT_WIDE lanes through ONE mpe_track_step_batch_wide (synchronous), advanced as collect_detect advances
+  // the narrow ones
+  int detect_wide() {
+    gather_items(OP_DETECT_WIDE, -1);
+    if (items.empty()) return MPE_OK;
+    const int m = (int)items.size();
+    wdets.resize((size_t)m);
+    corr.resize((size_t)m * 2 * MPE_MAX_MARKERS);
+    res.resize((size_t)m);
+    const int rc = mpe_track_step_batch_wide(h, items.data(), item_setup.data(), m, rows, cols, stride, frames_on_device ? 1 : 0,
+                                             encoding, big_endian, setups.data(), (int)setups.size(), wdets.data(),
+                                             corr.data(), res.data());
+    if (rc != MPE_OK) {
+      pend.clear();
+      return rc;
+    }
+    for (int k = 0; k < m; ++k) {
+      const mpe_detections_wide& d = wdets[(size_t)k];
+      advance(pend[(size_t)k], d.n, d.status, d.undist_xy, d.dist_xy, res[(size_t)k], &corr[(size_t)k * 2 * MPE_MAX_MARKERS],
+              true);
+    }
+    pend.clear();
+    return MPE_OK;
+  }
+
+  // the OP_BRUTE lanes that hold more than MPE_MAX_DETECTIONS points: mpe_solve_bruteforce_batch_wide, one call per
+  // set-up that has such lanes.  Under vote_arith 2 (no strict form) such a lane keeps MPE_FRAME_TOO_MANY_DETECTIONS
+  // and the other streams go on.
+  int brute_wide() {
+    for (size_t s = 0; s < setups.size(); ++s) {
+      std::vector<int> idx;
+      for (int i = 0; i < n; ++i)
+        if (L[(size_t)i].op == OP_BRUTE && lane_setup[(size_t)i] == (int)s && ts[i]->det.size() / 2 > (size_t)MPE_MAX_DETECTIONS)
+          idx.push_back(i);
+      if (idx.empty()) continue;
+      const int m = (int)idx.size();
+      const mpe_tracker* t0 = ts[idx[0]];  // (the set-up of these lanes)
+      int arith = 0;
+      (void)mpe_get_option(h, "vote_arith", &arith);
+      if (arith == 2 || n_markers(t0) < 1) {
+        for (int i : idx) {
+          ts[i]->used_bruteforce = true;
+          L[(size_t)i].op = OP_DONE;
+          if (arith == 2) L[(size_t)i].error = MPE_FRAME_TOO_MANY_DETECTIONS;
+        }
+        continue;
+      }
+      std::vector<double> det_xy((size_t)m * 2 * MPE_WIDE_DETECTIONS, 0.0);
+      std::vector<int> nd((size_t)m);
+      for (int k = 0; k < m; ++k) {
+        const mpe_tracker* t = ts[idx[(size_t)k]];
+        nd[(size_t)k] = (int)t->det.size() / 2;
+        std::memcpy(&det_xy[(size_t)k * 2 * MPE_WIDE_DETECTIONS], t->det.data(), t->det.size() * sizeof(double));
+      }
+      const size_t hw = (size_t)MPE_WIDE_DETECTIONS * MPE_MAX_MARKERS;
+      res.resize((size_t)m);
+      std::vector<uint32_t> hist((size_t)m * hw), bc((size_t)m * 2 * MPE_MAX_MARKERS);
+      const int rc = mpe_solve_bruteforce_batch_wide(h, det_xy.data(), nd.data(), m, t0->markers.data(), n_markers(t0), t0->K,
+                                                     &t0->p, res.data(), hist.data(), bc.data());
+      if (rc != MPE_OK) return rc;
+      for (int k = 0; k < m; ++k) {
+        const int i = idx[(size_t)k];
+        mpe_tracker* t = ts[i];
+        const mpe_result& r = res[(size_t)k];
+        t->used_bruteforce = true;
+        L[(size_t)i].op = OP_DONE;
+        if (r.status < 0) {
+          L[(size_t)i].error = r.status;
+          continue;
+        }
+        bool any_vote = false;  // initialise() keeps correspondences_ when the histogram is empty (:704-719)
+        for (size_t q = 0; q < hw; ++q) any_vote |= hist[(size_t)k * hw + q] != 0;
+        if (any_vote) {
+          t->n_corr = r.n_corr;
+          t->corr.assign(bc.begin() + (size_t)k * 2 * MPE_MAX_MARKERS, bc.begin() + (size_t)k * 2 * MPE_MAX_MARKERS + 2 * r.n_corr);
+        }
+        if (r.status == MPE_FRAME_POSE) take_result(t, r);
+      }
+    }
     return MPE_OK;
   }
 
@@ -662,6 +774,12 @@ struct BatchCtx {
   // mpe_solve_bruteforce_batch, the lanes of two or more set-ups through mpe_solve_bruteforce_batch_setups (with a
   // set-up without markers among them: one call per set-up, as it was)
   int brute() {
+    for (int i = 0; i < n; ++i)  // (more than MPE_MAX_DETECTIONS points only behind a wide detection)
+      if (L[(size_t)i].op == OP_BRUTE && ts[i]->det.size() / 2 > (size_t)MPE_MAX_DETECTIONS) {
+        const int rc = brute_wide();
+        if (rc != MPE_OK) return rc;
+        break;
+      }
     int n_with = 0;
     bool all_have_markers = true;  // (the _setups entry refuses a set-up without markers; alone it just finds no pose)
     std::vector<char> has(setups.size(), 0);
@@ -756,18 +874,21 @@ struct BatchCtx {
     int rc = collect_detect();
     if (rc != MPE_OK) return rc;
     for (;;) {
-      bool any_detect = false, any_brute = false;
+      bool any_detect = false, any_brute = false, any_wide = false;
       for (int i = 0; i < n; ++i) {
         any_detect |= L[(size_t)i].op == OP_DETECT;
         any_brute |= L[(size_t)i].op == OP_BRUTE;
+        any_wide |= L[(size_t)i].op == OP_DETECT_WIDE;
       }
-      if (!any_detect && !any_brute) break;
+      if (!any_detect && !any_brute && !any_wide) break;
       if (any_detect)
         for (int big = 0; big < 2; ++big) {
           const int m = submit_detect(big);
           if (m < 0) return m;
           if (m > 0 && (rc = collect_detect()) != MPE_OK) return rc;
         }
+      // (the glare lanes of this iteration, those the detections just collected turned up included, in one call)
+      if ((rc = detect_wide()) != MPE_OK) return rc;
       if ((rc = brute()) != MPE_OK) return rc;
     }
     return MPE_OK;

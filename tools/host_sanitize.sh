@@ -25,4 +25,10 @@ WP=$(mktemp -d)/wide_peel_host
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
     -I rpg_monocular_pose_estimator_amd/csrc tests/host/wide_peel_host.cpp -o $WP -L oracle -lmpe_oracle -Wl,-rpath,$R/oracle && $WP || rc=1
 rm -rf "$(dirname $WP)"
+# the nearest-neighbour correspondences of k_nn_wide (csrc/mpe_wide_nn.h), the 64-lane form against the plain double loop:
+# a stand-alone program too
+WN=$(mktemp -d)/wide_nn_host
+g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+    -I rpg_monocular_pose_estimator_amd/csrc tests/host/wide_nn_host.cpp -o $WN && $WN || rc=1
+rm -rf "$(dirname $WN)"
 exit $rc
