@@ -354,7 +354,8 @@ int mpe_track_step_batch_cancel(mpe_handle* h);
  * K / D (the reference: one PoseEstimator per camera, each with its own calibration and object,
  * pose_estimator.h:63,82-83, filled per node from that camera's camera_info, monocular_pose_estimator.cpp:103-120).
  * A set-up is one such camera + marker set + parameter set (n_markers 1 .. MPE_MAX_MARKERS); item i runs with
- * setups[item_setup[i]].  All items share rows / cols / stride.  Each item's records are byte-identical to those of
+ * setups[item_setup[i]].  All items share rows / cols / stride (items that differ in
+ * them: mpe_track_step_batch_formats below).  Each item's records are byte-identical to those of
  * mpe_track_step_batch over the items of its set-up alone.  Records come back in the caller's item order; the fused time
  * step stays ONE launch for the whole submission (set-ups of more than 8 markers, track_fused 0 and slots that overflow
  * the small blob tier run per set-up through the chain of kernels).  mpe_track_step_batch_collect / _cancel serve this
@@ -395,8 +396,8 @@ int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_ite
                                               int n_setups);
 /* mpe_track_step_batch_setups_device[_submit] for device frames in the camera's own ENCODING (a decoder or a DMA engine
  * that delivers bgr8, mono16, ... into device memory): `encoding` is one MPE_ENC_* value for the whole call, as rows,
- * cols and the stride are; src_big_endian has the meaning it has in mpe_convert_to_mono8 (read for MPE_ENC_MONO16
- * alone).  stride_bytes is in SOURCE bytes (Image.step); rows, cols and every ROI stay in pixels; items[i].img needs no
+ * cols and the stride are (items that differ in them: mpe_track_step_batch_formats below); src_big_endian has the
+ * meaning it has in mpe_convert_to_mono8 (read for MPE_ENC_MONO16 alone).  stride_bytes is in SOURCE bytes (Image.step); rows, cols and every ROI stay in pixels; items[i].img needs no
  * alignment.  The gather kernel decodes the pixels it gathers, by the rules stated at mpe_convert_to_mono8, so no mono8
  * copy of the frames is made and no separate conversion is launched: every detection record, correspondence row and
  * result is byte-identical to what mpe_track_step_batch_setups_device returns over the same frames after
@@ -414,6 +415,40 @@ int mpe_track_step_batch_setups_device_encoded(mpe_handle* h, const mpe_track_it
 int mpe_track_step_batch_setups_device_encoded_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup,
                                                       int n, int rows, int cols, size_t stride_bytes, int encoding,
                                                       int src_big_endian, const mpe_track_setup* setups, int n_setups);
+/* The lock-step time step of streams that differ in IMAGE FORMAT — one PoseEstimator per camera (pose_estimator.h:63,
+ * 82-83), each fed its own camera_info and its own image encoding (monocular_pose_estimator.cpp:103-126,147): a 752 x 480
+ * mono camera beside a 1920 x 1200 one, a bgr8 camera beside a mono16 one, one sensor behind drivers with different row
+ * padding.  Item i is an image of formats[item_format[i]] — rows, cols, the stride in SOURCE bytes (Image.step), one
+ * MPE_ENC_* value and, for MPE_ENC_MONO16 alone, the byte order — and runs with setups[item_setup[i]]; its ROI is in
+ * pixels of its own image.  item_format == NULL only with n_formats == 1, item_setup == NULL only with n_setups == 1.
+ * frames_on_device 0: items[i].img are host frames, packed with the item's own stride; every format that has items
+ * must be MPE_ENC_MONO8 (else MPE_ERR_ARG, the rule of mpe_track_step_batch_wide).  1: device frames; ONE gather kernel
+ * reads every item by its own format (stride, image end, decode) from a small format table that travels in the same
+ * host-to-device copy as the header and the gather table, so the submission is still one copy and one launch in front
+ * of the tracking launch.  A call whose items all have one format (equal formats count once) is handed to
+ * mpe_track_step_batch_setups_submit / mpe_track_step_batch_setups_device_encoded_submit as it is.  Every item's
+ * detections, correspondence rows and result equal, byte for byte, those of the entry of its kind over the items of its
+ * format alone (the slot size, the largest ROI of the call, does not enter the records).  mpe_track_step_batch_collect
+ * and _cancel serve this submit like every other one.
+ * Usage errors, all before any device work, the handle usable afterwards.  MPE_ERR_ARG: a null pointer; a format or
+ * set-up index out of range; rows < 1, cols < 1 or stride_bytes < cols * bytes per pixel; a ROI outside ITS OWN image
+ * (one that fits the largest image of the call but not the item's never reaches the gather); frames_on_device 1 and an
+ * img that does not lie, with its OWN encoded image — (rows - 1) * stride_bytes + cols * bytes per pixel —, inside one
+ * device allocation on the handle's device (host memory, pinned included); a submission that is not yet collected.
+ * MPE_ERR_UNSUPPORTED: an encoding outside the six.  n == 0: MPE_OK, nothing submitted. */
+typedef struct mpe_image_format {
+  int rows, cols;      /* pixels */
+  size_t stride_bytes; /* SOURCE bytes per row (Image.step) */
+  int encoding;        /* MPE_ENC_* */
+  int src_big_endian;  /* read for MPE_ENC_MONO16 alone */
+} mpe_image_format;
+int mpe_track_step_batch_formats_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup,
+                                        const int* item_format, int n, const mpe_image_format* formats, int n_formats,
+                                        int frames_on_device, const mpe_track_setup* setups, int n_setups);
+int mpe_track_step_batch_formats(mpe_handle* h, const mpe_track_item* items, const int* item_setup, const int* item_format,
+                                 int n, const mpe_image_format* formats, int n_formats, int frames_on_device,
+                                 const mpe_track_setup* setups, int n_setups, mpe_detections* dets_out, uint32_t* corr_out,
+                                 mpe_result* out);
 /* mpe_solve_bruteforce for N detection sets in one submission (the re-initialisations of a lock-step batch):
  * det_xy n x MPE_MAX_DETECTIONS x 2 (n_det[i] valid rows); hist (optional) n x MPE_MAX_DETECTIONS x
  * MPE_MAX_MARKERS, corr (optional) n x 2*MPE_MAX_MARKERS. */
@@ -621,6 +656,25 @@ int mpe_tracker_run_sequences_batch_device_encoded_threads(mpe_tracker* const* t
                                                            size_t stride_bytes, size_t frame_stride_bytes, int encoding,
                                                            int src_big_endian, const double* times, mpe_result* out,
                                                            int* info, int n_threads);
+
+/* mpe_tracker_estimate_batch_mixed / mpe_tracker_run_sequences_batch_mixed_threads (frames_on_device 0: host frames,
+ * every format MPE_ENC_MONO8) and their _device_encoded forms (frames_on_device 1) for trackers whose cameras differ in
+ * image format as well: formats[i] is stream i's (mpe_image_format above), frame_stride_bytes[i] its sequence stride in
+ * source bytes.  The _mixed rules hold — distinct trackers, one handle per group, for _threads the groups by handle,
+ * pipelined as before.  Whole-image ROI, determineROI, the size class and the whole-image retry of a stream use that
+ * stream's rows and cols; the detections of a time step go through ONE mpe_track_step_batch_formats_submit (equal
+ * formats once in its table), the rare wide re-detections through one mpe_track_step_batch_wide per distinct format
+ * among those streams, the re-initialisations through the brute-force entries as before (they work on detections).
+ * Results are identical to mpe_tracker_estimate per stream and to the entries above over each format's trackers alone.
+ * A null pointer, a bad format (rows, cols, stride) or an encoded format with host frames is MPE_ERR_ARG, an encoding
+ * outside the six MPE_ERR_UNSUPPORTED, all before any tracker is touched. */
+int mpe_tracker_estimate_batch_formats(mpe_tracker* const* trackers, int n, const uint8_t* const* imgs, int frames_on_device,
+                                       const mpe_image_format* formats, const double* times, mpe_result* out, int* info,
+                                       int* updated);
+int mpe_tracker_run_sequences_batch_formats_threads(mpe_tracker* const* trackers, int n, const uint8_t* const* frames,
+                                                    int n_frames, int frames_on_device, const mpe_image_format* formats,
+                                                    const size_t* frame_stride_bytes, const double* times, mpe_result* out,
+                                                    int* info, int n_threads);
 
 /* The estimator's private state (pose_estimator.h:56-62, 74-79), for callers that drive the public
  * step methods of the class (predictPose, findCorrespondences, ... — see compat/) between calls of

@@ -12,7 +12,8 @@ from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYP
                       estimate_batch_multi_device_gather, ENCODINGS,
                       tracker_estimate_batch, tracker_run_sequences_batch, tracker_estimate_batch_mixed,
                       tracker_run_sequences_batch_mixed, PinnedFrames, tracker_estimate_batch_device,
-                      tracker_run_sequences_batch_device)
+                      tracker_run_sequences_batch_device, ImageFormat, tracker_estimate_batch_formats,
+                      tracker_run_sequences_batch_formats)
 from .pose_estimator import PoseEstimator  # noqa: F401
 
 __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE", "DETECTIONS_DTYPE",
@@ -22,4 +23,5 @@ __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE"
            "exponential_map", "logarithm_map", "predict_pose", "project_points", "find_correspondences",
            "shard_bounds", "estimate_batch_multi", "estimate_batch_multi_device_gather", "ENCODINGS", "tracker_estimate_batch", "tracker_run_sequences_batch", "tracker_estimate_batch_mixed",
            "tracker_run_sequences_batch_mixed", "PinnedFrames", "tracker_estimate_batch_device",
-           "tracker_run_sequences_batch_device"]
+           "tracker_run_sequences_batch_device", "ImageFormat", "tracker_estimate_batch_formats",
+           "tracker_run_sequences_batch_formats"]

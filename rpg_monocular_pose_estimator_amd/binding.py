@@ -234,6 +234,16 @@ def load_library():
     lib.mpe_tracker_estimate_batch_device_encoded.argtypes = a[:6] + enc + a[6:]
     a = lib.mpe_tracker_run_sequences_batch_threads.argtypes
     lib.mpe_tracker_run_sequences_batch_device_encoded_threads.argtypes = a[:8] + enc + a[8:]
+    # ... every item / stream in an image format of its own (mpe_image_format)
+    lib.mpe_track_step_batch_formats.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                                 C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+    lib.mpe_track_step_batch_formats_submit.argtypes = lib.mpe_track_step_batch_formats.argtypes[:10]
+    lib.mpe_tracker_estimate_batch_formats.argtypes = [hp, C.c_int, hp, C.c_int, C.c_void_p, dp, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
+    lib.mpe_tracker_run_sequences_batch_formats_threads.argtypes = [hp, C.c_int, hp, C.c_int, C.c_int, C.c_void_p,
+                                                                    C.POINTER(C.c_size_t), dp, C.c_void_p, C.c_void_p,
+                                                                    C.c_int]
     lib.mpe_shard_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.mpe_shard_bounds.restype = None
     lib.mpe_estimate_batch_multi.argtypes = [hp, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
@@ -386,6 +396,108 @@ def tracker_run_sequences_batch_device(trackers, frames, times, threads=1, encod
                                     fstride, times, threads)
     return _run_sequences_batch("mpe_tracker_run_sequences_batch_device_encoded_threads", trackers, ptrs, n, rows, cols,
                                 stride, fstride, times, threads, _enc_args(encoding, big_endian))
+
+
+class ImageFormat(C.Structure):  # mpe_image_format
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("stride_bytes", C.c_size_t), ("encoding", C.c_int),
+                ("src_big_endian", C.c_int)]
+
+    def key(self):
+        """What makes two formats the same images (the byte order counts for mono16 alone)."""
+        return (self.rows, self.cols, self.stride_bytes, self.encoding,
+                bool(self.src_big_endian) if self.encoding == ENCODINGS["mono16"] else False)
+
+
+def _image_format(img, lead, spec):
+    """One image (lead 0) or sequence (lead 1: frames in front) of a *_formats entry: a numpy array (host) or a torch
+    CUDA tensor (device).  spec: an ImageFormat, taken as it is; or an encoding name / (name, big_endian) / None
+    ("mono8"), and the format is read off the array — (rows, cols) uint8 for mono8, (rows, cols, bytes per pixel) uint8
+    or, mono16, (rows, cols) uint16 / int16 for the other encodings, pixels contiguous within a row.
+    -> (ImageFormat, address, frame stride in bytes (lead 1, else 0))."""
+    dev = _is_torch(img)
+    es = img.element_size() if dev else img.itemsize
+    strides = [x * es for x in img.stride()] if dev else list(img.strides)
+    ptr = img.data_ptr() if dev else img.ctypes.data
+    fstride = strides[0] if lead else 0
+    if isinstance(spec, ImageFormat):
+        return spec, ptr, fstride
+    name, big = (spec, False) if spec is None or isinstance(spec, str) else spec
+    name = name or "mono8"
+    if name not in ENCODINGS:
+        raise MpeError("encoding %r: one of %s" % (name, ", ".join(sorted(ENCODINGS))))
+    bpp = {"mono8": 1, "mono16": 2, "bgr8": 3, "rgb8": 3}.get(name, 4)
+    shape, nd = tuple(img.shape), len(img.shape)
+    if es == 1 and bpp > 1:
+        ok = nd == lead + 3 and shape[-1] == bpp and strides[-1] == 1 and strides[-2] == bpp
+    else:
+        ok = es == min(bpp, 2) and bpp <= 2 and nd == lead + 2 and strides[-1] == es
+    if not ok:
+        raise MpeError("%s frames: (rows, cols) uint8 for mono8, (rows, cols, bytes per pixel) uint8 or, mono16, (rows, cols) "
+                       "uint16 / int16 for the other encodings, pixels contiguous within a row" % name)
+    return (ImageFormat(int(shape[lead]), int(shape[lead + 1]), int(strides[lead]), ENCODINGS[name], int(bool(big))), ptr,
+            fstride)
+
+
+def _stream_formats(imgs, lead, formats):
+    """The images (or sequences) of the streams of a *_formats entry, which may differ in shape and strides: all numpy
+    (host) or all torch CUDA tensors on one device (work queued on torch's current stream there is waited for).
+    -> (frames_on_device, addresses, [ImageFormat], frame strides)."""
+    imgs = list(imgs)
+    on_device = _is_torch(imgs[0])
+    if on_device:
+        import torch
+        if not all(_is_torch(t) and t.is_cuda and t.device == imgs[0].device for t in imgs):
+            raise MpeError("device frames: torch CUDA tensors on one device are needed (no mix with host frames)")
+        torch.cuda.current_stream(imgs[0].device).synchronize()
+    elif any(_is_torch(t) for t in imgs):
+        raise MpeError("host frames: numpy arrays are needed (no mix with device frames)")
+    specs = [None] * len(imgs) if formats is None else list(formats)
+    assert len(specs) == len(imgs)
+    got = [_image_format(im, lead, sp) for im, sp in zip(imgs, specs)]
+    return int(on_device), [g[1] for g in got], [g[0] for g in got], [g[2] for g in got]
+
+
+def tracker_estimate_batch_formats(trackers, imgs, times, formats=None):
+    """mpe_tracker_estimate_batch_formats: one lock-step time step of distinct trackers on ONE handle whose cameras may
+    differ in image size, row stride and encoding (and in camera, markers and parameters).  imgs: a list of numpy arrays
+    (host frames, mono8) or of torch CUDA tensors (device frames), one per tracker, of any shapes.  formats: None (mono8
+    formats read off the arrays), or per tracker an encoding name, (name, big_endian) or an ImageFormat.
+    -> (records (N), info (N,8), updated (N) bool), those of the existing entries over each format's trackers alone."""
+    lib = load_library()
+    n = len(trackers)
+    on_device, ptrs, fmts, _ = _stream_formats(imgs, 0, formats)
+    assert len(ptrs) == n
+    ts = (C.c_void_p * n)(*[t._t for t in trackers])
+    times = _f64(times).reshape(-1)
+    rec, info, upd = np.zeros(n, RESULT_DTYPE), np.zeros((n, 8), np.int32), np.zeros(n, np.int32)
+    rc = lib.mpe_tracker_estimate_batch_formats(ts, n, (C.c_void_p * n)(*ptrs), on_device, (ImageFormat * n)(*fmts), _dp(times),
+                                                rec.ctypes.data, info.ctypes.data, upd.ctypes.data)
+    if rc < 0:
+        raise MpeError("mpe_tracker_estimate_batch_formats failed (%d): %s"
+                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
+    return rec, info, upd.astype(bool)
+
+
+def tracker_run_sequences_batch_formats(trackers, frames, times, threads=1, formats=None):
+    """mpe_tracker_run_sequences_batch_formats_threads: the lock-step loop in C over sequences that may differ in image
+    size, row stride, frame stride and encoding.  frames: a list of (n, rows, cols[, bytes per pixel]) numpy arrays
+    (host, mono8) or torch CUDA tensors (device), one sequence per tracker, the same n; formats as in
+    tracker_estimate_batch_formats.  Each handle's trackers form one lock-step group.  -> (records (N,n), info (N,n,8))."""
+    lib = load_library()
+    N = len(trackers)
+    on_device, ptrs, fmts, fstrides = _stream_formats(frames, 1, formats)
+    n = int(frames[0].shape[0])
+    assert len(ptrs) == N and all(int(f.shape[0]) == n for f in frames)
+    ts = (C.c_void_p * N)(*[t._t for t in trackers])
+    times = _f64(times).reshape(-1)
+    rec, info = np.zeros((N, n), RESULT_DTYPE), np.zeros((N, n, 8), np.int32)
+    rc = lib.mpe_tracker_run_sequences_batch_formats_threads(ts, N, (C.c_void_p * N)(*ptrs), n, on_device,
+                                                             (ImageFormat * N)(*fmts), (C.c_size_t * N)(*fstrides),
+                                                             _dp(times), rec.ctypes.data, info.ctypes.data, int(threads))
+    if rc < 0:
+        raise MpeError("mpe_tracker_run_sequences_batch_formats_threads failed (%d): %s"
+                       % (rc, lib.mpe_last_error(trackers[0]._handle._h).decode()))
+    return rec, info
 
 
 class TrackItem(C.Structure):  # mpe_track_item
@@ -860,7 +972,8 @@ class Handle:
                     undist=np.array(det.undist_xy[:2 * n]).reshape(-1, 2), gn_iterations=res.gn_iterations)
 
     # ---- one lock-step time step of N streams: mpe_track_step_batch_setups[_device] ----------------------
-    def _track_step_batch(self, entry, ptrs, rows, cols, stride, rois, predicted_px, setups, item_setup, enc=()):
+    def _track_step_batch(self, entry, ptrs, rows, cols, stride, rois, predicted_px, setups, item_setup, enc=(),
+                          formats=None):
         n = len(ptrs)
         keep = []
         su = (TrackSetup * len(setups))()
@@ -879,9 +992,11 @@ class Handle:
         dets = np.zeros(n, DETECTIONS_WIDE_DTYPE if wide else DETECTIONS_DTYPE)
         corr = np.zeros((n, MAX_MARKERS, 2), np.uint32)
         res = np.zeros(n, RESULT_DTYPE)
-        rc = getattr(self._lib, entry)(self._h, items, idx, n, rows, cols, C.c_size_t(stride), *enc, su, len(setups),
-                                       C.c_void_p(dets.ctypes.data), C.c_void_p(corr.ctypes.data),
-                                       C.c_void_p(res.ctypes.data))
+        # (formats: (item_format, format table, frames_on_device) in place of one shape, stride and encoding)
+        shape = (n, rows, cols, C.c_size_t(stride)) + tuple(enc) if formats is None else \
+            (formats[0], n, formats[1], len(formats[1]), formats[2])
+        rc = getattr(self._lib, entry)(self._h, items, idx, *shape, su, len(setups), C.c_void_p(dets.ctypes.data),
+                                       C.c_void_p(corr.ctypes.data), C.c_void_p(res.ctypes.data))
         self._check(rc, entry)
         return dets, corr, res
 
@@ -912,6 +1027,29 @@ class Handle:
                                          predicted_px, setups, item_setup, _enc_args(encoding, big_endian))
         del keep
         return out
+
+    def track_step_batch_formats(self, imgs, rois, predicted_px, setups, item_setup=None, formats=None, item_format=None):
+        """mpe_track_step_batch_formats: one time step of N streams whose images may differ in size, row stride and
+        encoding, in ONE submission.  imgs: N numpy arrays (host frames, mono8) or N torch CUDA tensors on this handle's
+        device, of any shapes; rois in pixels of the item's own image; formats: None (mono8 formats read off the arrays),
+        or per item an encoding name, (name, big_endian) or an ImageFormat — equal ones share an entry of the format
+        table.  With item_format, formats is the table itself (ImageFormat entries) and item_format[i] item i's index.
+        item_setup None: one set-up for all.  -> (detections, correspondences, records) as track_step_batch: every item's
+        are those of track_step_batch / track_step_batch_device over the items of its format alone."""
+        if item_format is None:
+            on_device, ptrs, fmts, _ = _stream_formats(imgs, 0, formats)
+            table, index = [], {}
+            item_format = [index.setdefault(f.key(), len(index)) for f in fmts]
+            for f, k in zip(fmts, item_format):
+                if k == len(table):
+                    table.append(f)
+        else:
+            on_device, ptrs, _, _ = _stream_formats(imgs, 0, [formats[k] for k in item_format])
+            table = list(formats)
+        n = len(ptrs)
+        ifmt = None if len(table) == 1 else (C.c_int * n)(*[int(k) for k in item_format])
+        return self._track_step_batch("mpe_track_step_batch_formats", ptrs, 0, 0, 0, rois, predicted_px, setups, item_setup,
+                                      formats=(ifmt, (ImageFormat * len(table))(*table), on_device))
 
     def track_step_batch_wide(self, imgs, rois, predicted_px, setups, item_setup=None, encoding="mono8", big_endian=False):
         """mpe_track_step_batch_wide: track_step_batch / track_step_batch_device with records of WIDE_DETECTIONS points

@@ -12,6 +12,11 @@
 // slot bytes are 16 PIXELS of the ROI row, decoded from 2 (mono16), 3 (bgr8 / rgb8) or 4 (bgra8 / rgba8) source bytes
 // each by the rules of mpe_pixel.h — the bytes mpe_convert_to_mono8 would have written into a mono8 copy of the frame.
 // x, y, w, h stay in pixels; stride and img_bytes are source bytes.
+//
+// gather_segment_format is the segment of a submission whose items differ in image format (k_gather_rois_formats):
+// stride, image end, bytes per pixel and channel / byte order come from the item's entry of a format table, and the
+// segment is the one of the two functions above that the entry names.  Every property stated above holds per item,
+// against the item's OWN image end.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -32,9 +37,20 @@ struct GatherItem {
   const uint8_t* img;  // device image of the stream
   int x, y, w, h;      // ROI, inside the image
   int slot;            // destination slot
-  int pad_;
+  int format;          // index into the submission's GatherFormat table (k_gather_rois_formats alone reads it)
 };
 static_assert(sizeof(GatherItem) == 32, "table entries of 32 bytes");
+
+// one distinct image format of a submission (device table behind the items')
+struct GatherFormat {
+  uint64_t stride;     // source bytes per row
+  uint64_t img_bytes;  // the image ends with the last pixel of its last row: (rows - 1) * stride + cols * bpp
+  int bpp;             // source bytes per pixel: 1 mono8, 2 mono16, 3 bgr8 / rgb8, 4 bgra8 / rgba8
+  int rgb;             // colour pixels are R G B [A] (else B G R [A])
+  int big_endian;      // the mono16 values are
+  int pad_;
+};
+static_assert(sizeof(GatherFormat) == 32, "table entries of 32 bytes");
 
 // plain loads (on the device from the global address space: global_load instead of flat_load); the host test
 // substitutes loads that check their address against the image
@@ -153,6 +169,27 @@ __host__ __device__ inline void gather_segment_encoded(const Loads& mem, const u
     for (int b = 0; b < 4; ++b)
       if (4 * i + b < n) v |= px[4 * i + b] << (8 * b);  // (pixels beyond the ROI row hold whatever lay behind it)
     out[i] = v;
+  }
+}
+
+// the same 16 slot bytes from an image of format f: the segment function f names
+template <class Loads>
+__host__ __device__ inline void gather_segment_format(const Loads& mem, const uint8_t* img, const GatherFormat& f, int x, int y,
+                                                      int w, int h, int r, int seg, uint32_t out[4]) {
+  const size_t stride = (size_t)f.stride, img_bytes = (size_t)f.img_bytes;
+  switch (f.bpp) {
+    case 1:
+      gather_segment(mem, img, img_bytes, stride, x, y, w, h, r, seg, out);
+      break;
+    case 2:
+      gather_segment_encoded<2>(mem, img, img_bytes, stride, x, y, w, h, r, seg, false, f.big_endian != 0, out);
+      break;
+    case 3:
+      gather_segment_encoded<3>(mem, img, img_bytes, stride, x, y, w, h, r, seg, f.rgb != 0, false, out);
+      break;
+    default:
+      gather_segment_encoded<4>(mem, img, img_bytes, stride, x, y, w, h, r, seg, f.rgb != 0, false, out);
+      break;
   }
 }
 

@@ -35,6 +35,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
 
 namespace mpe {
 struct GatherItem;  // (mpe_gather.h)
+struct GatherFormat;
 }
 using namespace mpe;
 
@@ -307,6 +308,10 @@ __attribute__((visibility("hidden"))) hipError_t launch_gather_rois(const Gather
 // bytes, the ROIs of the table in pixels): the gather decodes what it reads (k_gather_rois_encoded)
 __attribute__((visibility("hidden"))) hipError_t launch_gather_rois_encoded(const GatherItem* tab, int n, uint8_t* dst, const FrameGeom& g, size_t stride,
                                       size_t img_bytes, int encoding, int big_endian, hipStream_t s);
+// the same slots from images that differ in format: item e is an image of fmts[tab[e].format] (device table, every index
+// below its length — the submission builds both; k_gather_rois_formats)
+__attribute__((visibility("hidden"))) hipError_t launch_gather_rois_formats(const GatherItem* tab, const GatherFormat* fmts, int n, uint8_t* dst,
+                                      const FrameGeom& g, hipStream_t s);
 // the text of mpe_last_error, for mpe_tracker.cpp (which sees only the C ABI and declares this itself; mpe_options.cpp)
 void set_error(mpe_handle* h, const char* what);
 }  // namespace mpe_host

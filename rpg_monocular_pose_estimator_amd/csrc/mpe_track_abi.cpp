@@ -1,5 +1,6 @@
 // mpe_track_abi.cpp — host side of libmpe_hip.so, part 3 (see mpe_host.h): one tracked frame (mpe_track_step) and the
-// lock-step time step of N camera streams (mpe_track_step_batch[_setups][_device[_encoded]][_submit / _collect / _cancel]); the
+// lock-step time step of N camera streams (mpe_track_step_batch[_setups][_device[_encoded]][_submit / _collect / _cancel],
+// mpe_track_step_batch_formats[_submit] for streams that differ in image size, stride and encoding); the
 // per-stream state machine on top of them is mpe_tracker.cpp.  Every entry checks its own arguments and then makes the
 // same submission (submit_slots): a uniform batch is the submission of one set-up, a tracked frame a batch of one, and
 // frames in device memory differ only in where the ROI slots come from (a gather kernel instead of a host copy; for
@@ -66,13 +67,16 @@ void pack_roi(uint8_t* slot, const FrameGeom& g, const mpe_track_item& it, size_
 // stands between a caller's mistake and a GPU fault.  Each distinct allocation is looked up once per call (the frames
 // of N streams usually sit in one or a few).  (static, as prepare_setups below: inside extern "C" the unnamed namespace
 // alone does not keep a name out of the library's exports, and these two are no part of them)
-static int check_device_images(mpe_handle* h, const mpe_track_item* items, int n, size_t img_bytes) {
+// item_bytes (n values, or null: img_bytes for all): every item's OWN image extent.
+static int check_device_images(mpe_handle* h, const mpe_track_item* items, int n, size_t img_bytes,
+                               const size_t* item_bytes = nullptr) {
   struct Span {
     uintptr_t lo, hi;
   };
   std::vector<Span> ok;
   for (int i = 0; i < n; ++i) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(items[i].img);
+    if (item_bytes) img_bytes = item_bytes[i];
     bool known = false;
     for (const Span& s : ok) known |= a >= s.lo && a + img_bytes <= s.hi;
     if (known) continue;
@@ -166,11 +170,22 @@ int track_range_chain(mpe_handle* h, const mpe_handle::PendingTrack::Range& r, i
 // wide (mpe_track_step_batch_wide): the same slots, header and gather, nothing launched behind them — no range is fused,
 // the header also carries one identity work-list per range for the general blob tier, the record area is sized for
 // WideTrackRecords, and the submission is not left pending: run_wide_slots works it off synchronously.
-enum PixelSource { kHostFrames, kDeviceFrames, kEncodedDeviceFrames };
+// formats (mpe_track_step_batch_formats): every item has an image format of its own — fm->item_format[i] indexes
+// fm->formats, the distinct formats of the submission.  Host frames are packed with the item's stride; of device frames
+// the header carries the format table behind the gather table and k_gather_rois_formats decodes every item by its own
+// entry.  Within a set-up range the slots are then ordered by format (stable), so the gather's branch on the format
+// diverges only in the waves that hold a slot boundary between two formats.
+enum PixelSource { kHostFrames, kDeviceFrames, kEncodedDeviceFrames, kFormatDeviceFrames };
+struct SlotFormats {
+  const int* item_format;           // n indices into formats
+  const mpe_image_format* formats;  // distinct, checked
+  int n_formats;
+};
 
 int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, const FrameGeom& g,
                  size_t stride_bytes, const TrackSetup* setups, int n_setups, PixelSource source = kHostFrames,
-                 size_t img_bytes = 0, int encoding = MPE_ENC_MONO8, int big_endian = 0, bool wide = false) {
+                 size_t img_bytes = 0, int encoding = MPE_ENC_MONO8, int big_endian = 0, bool wide = false,
+                 const SlotFormats* fm = nullptr) {
   const bool on_device = source != kHostFrames;
   mpe_handle::PendingTrack& pt = h->pending_track;
   pt.t_in = h->track_profile ? clk::now() : clk::time_point();
@@ -198,7 +213,12 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     const int r = range_of[(size_t)setup_of(i)];
     pt.perm[(size_t)(pt.ranges[(size_t)r].begin + fill[(size_t)r]++)] = i;
   }
-  // [predictions | windows | set-up table | slot -> set-up | gather table (device frames) | ROI slots] in slot order; one
+  if (fm)
+    for (const mpe_handle::PendingTrack::Range& r : pt.ranges)
+      std::stable_sort(pt.perm.begin() + r.begin, pt.perm.begin() + r.begin + r.count,
+                       [fm](int a, int b) { return fm->item_format[a] < fm->item_format[b]; });
+  // [predictions | windows | set-up table | slot -> set-up | gather table (device frames) | format table (device frames
+  // of several formats) | ROI slots] in slot order; one
   // H2D copy carries what the host has of it: all of it, or the header in front of the slots.  The set-up table only for
   // a launch of two or more set-ups: one set-up goes as kernel arguments (the table instantiation is 5.6 % slower)
   const bool table = fused_setups >= 2;
@@ -210,7 +230,9 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   const size_t list_off = pred_bytes + win_bytes + tab_bytes + idx_bytes;
   const size_t list_bytes = wide ? (((size_t)n + pt.ranges.size()) * sizeof(int) + 15) & ~(size_t)15 : 0;
   const size_t gat_off = list_off + list_bytes;
-  const size_t head_bytes = gat_off + (on_device ? (size_t)n * sizeof(GatherItem) : 0);  // (a multiple of 16: the slots' alignment)
+  const size_t fmt_off = gat_off + (on_device ? (size_t)n * sizeof(GatherItem) : 0);
+  const size_t head_bytes =  // (a multiple of 16: the slots' alignment)
+      fmt_off + (source == kFormatDeviceFrames ? (size_t)fm->n_formats * sizeof(GatherFormat) : 0);
   const size_t in_bytes = head_bytes + (size_t)n * slot;
   const size_t staged_bytes = on_device ? head_bytes : in_bytes;
   const size_t rec_bytes = wide ? WideTrackRecords::bytes(n) : TrackRecords::bytes(n);
@@ -248,9 +270,20 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     wins[4 * k + 2] = it.roi_x;
     wins[4 * k + 3] = it.roi_y;
     if (on_device)
-      gat[k] = GatherItem{it.img, it.roi_x, it.roi_y, it.roi_w, it.roi_h, k, 0};
+      gat[k] = GatherItem{it.img, it.roi_x, it.roi_y, it.roi_w, it.roi_h, k, fm ? fm->item_format[i] : 0};
     else
-      pack_roi(mb + head_bytes + (size_t)k * slot, g, it, stride_bytes);
+      pack_roi(mb + head_bytes + (size_t)k * slot, g, it, fm ? fm->formats[fm->item_format[i]].stride_bytes : stride_bytes);
+  }
+  if (source == kFormatDeviceFrames) {
+    GatherFormat* tab = reinterpret_cast<GatherFormat*>(mb + fmt_off);
+    for (int f = 0; f < fm->n_formats; ++f) {
+      const mpe_image_format& mf = fm->formats[f];
+      const int bpp = encoding_bytes_per_pixel(mf.encoding);
+      tab[f] = GatherFormat{(uint64_t)mf.stride_bytes,
+                            (uint64_t)((size_t)(mf.rows - 1) * mf.stride_bytes + (size_t)mf.cols * (size_t)bpp), bpp,
+                            mf.encoding == MPE_ENC_RGB8 || mf.encoding == MPE_ENC_RGBA8,
+                            mf.encoding == MPE_ENC_MONO16 && mf.src_big_endian, 0};
+    }
   }
   uint8_t* host_rec = mb + ((staged_bytes + 255) & ~(size_t)255);
   if ((rc = reserve_track(h, g, n, in_bytes)) != MPE_OK) return rc;
@@ -279,6 +312,10 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   else if (source == kEncodedDeviceFrames)
     HIP_TRY(h, launch_gather_rois_encoded(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g,
                                           stride_bytes, img_bytes, encoding, big_endian, h->stream));
+  else if (source == kFormatDeviceFrames)
+    HIP_TRY(h, launch_gather_rois_formats(reinterpret_cast<const GatherItem*>(d_in + gat_off),
+                                          reinterpret_cast<const GatherFormat*>(d_in + fmt_off), n, d_in + head_bytes, g,
+                                          h->stream));
   if (wide) {
     h->pending_track_rec = host_rec;  // (for run_wide_slots, which follows at once: nothing stays pending)
     return MPE_OK;
@@ -317,9 +354,11 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
 // What the _setups entries (host and device frames) check behind their own argument condition, every usage error before
 // any device work: no submission in flight, the set-ups, every item's set-up index and ROI (item_setup null: set-up 0);
 // then the slot geometry g and the prepared parameters of the set-ups that have streams.  n == 0: MPE_OK with nothing
-// prepared — there is nothing to submit.
+// prepared — there is nothing to submit.  fm: every item's ROI against its OWN image, fm->formats[fm->item_format[i]]
+// (rows and cols are not read).
 static int prepare_setups(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows, int cols,
-                          const mpe_track_setup* setups, int n_setups, FrameGeom& g, std::vector<TrackSetup>& prep) {
+                          const mpe_track_setup* setups, int n_setups, FrameGeom& g, std::vector<TrackSetup>& prep,
+                          const SlotFormats* fm = nullptr) {
   if (h->pending_track_n) return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
   for (int s = 0; s < n_setups; ++s) {
     const mpe_track_setup& su = setups[s];
@@ -332,6 +371,10 @@ static int prepare_setups(mpe_handle* h, const mpe_track_item* items, const int*
   for (int i = 0; i < n; ++i) {
     const int s = item_setup ? item_setup[i] : 0;
     if (s < 0 || s >= n_setups) return fail(h, MPE_ERR_ARG, "set-up index out of range");
+    if (fm) {
+      rows = fm->formats[fm->item_format[i]].rows;
+      cols = fm->formats[fm->item_format[i]].cols;
+    }
     if (!items[i].img || !roi_inside(items[i], rows, cols)) return fail(h, MPE_ERR_ARG, "ROI outside the image");
     used[(size_t)s] = 1;
     rmax = std::max(rmax, items[i].roi_h);
@@ -441,6 +484,83 @@ int mpe_track_step_batch_setups_device_encoded(mpe_handle* h, const mpe_track_it
   if (!dets_out || !corr_out || !out) return fail(h, MPE_ERR_ARG, "bad argument");
   const int rc = mpe_track_step_batch_setups_device_encoded_submit(h, items, item_setup, n, rows, cols, stride_bytes, encoding,
                                                                    src_big_endian, setups, n_setups);
+  if (rc != MPE_OK) return rc;
+  if (n == 0) return MPE_OK;  // (nothing was submitted)
+  return mpe_track_step_batch_collect(h, dets_out, corr_out, out);
+}
+
+namespace {
+// two formats name the same images: size, stride, encoding and — for mono16, which alone reads it — the byte order
+bool same_format(const mpe_image_format& a, const mpe_image_format& b) {
+  return a.rows == b.rows && a.cols == b.cols && a.stride_bytes == b.stride_bytes && a.encoding == b.encoding &&
+         (a.encoding != MPE_ENC_MONO16 || (a.src_big_endian != 0) == (b.src_big_endian != 0));
+}
+}  // namespace
+
+int mpe_track_step_batch_formats_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup,
+                                        const int* item_format, int n, const mpe_image_format* formats, int n_formats,
+                                        int frames_on_device, const mpe_track_setup* setups, int n_setups) {
+  // every usage error before any device work
+  if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || !formats || n_formats < 1 ||
+      (!item_format && n_formats != 1))
+    return fail(h, MPE_ERR_ARG, "bad argument");
+  for (int f = 0; f < n_formats; ++f) {
+    const size_t bpp = (size_t)encoding_bytes_per_pixel(formats[f].encoding);
+    if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+    if (formats[f].rows < 1 || formats[f].cols < 1 || formats[f].stride_bytes < (size_t)formats[f].cols * bpp)
+      return fail(h, MPE_ERR_ARG, "bad argument");
+  }
+  // the distinct formats that have items, in order of first use, and every item's index among them
+  std::vector<mpe_image_format> used;
+  std::vector<int> dense((size_t)n_formats, -1), item_dense((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const int f = item_format ? item_format[i] : 0;
+    if (f < 0 || f >= n_formats) return fail(h, MPE_ERR_ARG, "format index out of range");
+    if (dense[(size_t)f] < 0) {
+      if (!frames_on_device && formats[f].encoding != MPE_ENC_MONO8)
+        return fail(h, MPE_ERR_ARG, "host frames are mono8 (the encodings are decoded from device frames)");
+      size_t k = 0;
+      while (k < used.size() && !same_format(used[k], formats[f])) ++k;
+      if (k == used.size()) used.push_back(formats[f]);
+      dense[(size_t)f] = (int)k;
+    }
+    item_dense[(size_t)i] = dense[(size_t)f];
+  }
+  if (used.size() <= 1) {  // one format (or no item): the entry of that format, unchanged
+    const mpe_image_format& f = used.empty() ? formats[0] : used[0];
+    if (frames_on_device)
+      return mpe_track_step_batch_setups_device_encoded_submit(h, items, item_setup, n, f.rows, f.cols, f.stride_bytes,
+                                                               f.encoding, f.src_big_endian, setups, n_setups);
+    const std::vector<int> zero((size_t)n + 1, 0);  // (the host entry wants an index per item)
+    return mpe_track_step_batch_setups_submit(h, items, item_setup ? item_setup : zero.data(), n, f.rows, f.cols,
+                                              f.stride_bytes, setups, n_setups);
+  }
+  const SlotFormats fm = {item_dense.data(), used.data(), (int)used.size()};
+  FrameGeom g;
+  std::vector<TrackSetup> prep;
+  int rc = prepare_setups(h, items, item_setup, n, 0, 0, setups, n_setups, g, prep, &fm);
+  if (rc != MPE_OK) return rc;
+  ENTER(h);
+  if (!frames_on_device)
+    return submit_slots(h, items, item_setup, n, g, 0, prep.data(), n_setups, kHostFrames, 0, MPE_ENC_MONO8, 0, false, &fm);
+  std::vector<size_t> item_bytes((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const mpe_image_format& f = used[(size_t)item_dense[(size_t)i]];
+    item_bytes[(size_t)i] =
+        (size_t)(f.rows - 1) * f.stride_bytes + (size_t)f.cols * (size_t)encoding_bytes_per_pixel(f.encoding);
+  }
+  if ((rc = check_device_images(h, items, n, 0, item_bytes.data())) != MPE_OK) return rc;
+  return submit_slots(h, items, item_setup, n, g, 0, prep.data(), n_setups, kFormatDeviceFrames, 0, MPE_ENC_MONO8, 0, false,
+                      &fm);
+}
+
+int mpe_track_step_batch_formats(mpe_handle* h, const mpe_track_item* items, const int* item_setup, const int* item_format,
+                                 int n, const mpe_image_format* formats, int n_formats, int frames_on_device,
+                                 const mpe_track_setup* setups, int n_setups, mpe_detections* dets_out, uint32_t* corr_out,
+                                 mpe_result* out) {
+  if (!dets_out || !corr_out || !out) return fail(h, MPE_ERR_ARG, "bad argument");
+  const int rc = mpe_track_step_batch_formats_submit(h, items, item_setup, item_format, n, formats, n_formats,
+                                                     frames_on_device, setups, n_setups);
   if (rc != MPE_OK) return rc;
   if (n == 0) return MPE_OK;  // (nothing was submitted)
   return mpe_track_step_batch_collect(h, dets_out, corr_out, out);

@@ -3,7 +3,8 @@
 // host and copy them, k_gather_rois writes them from the caller's device images.  The slot bytes are those pack_roi
 // writes, so everything behind them is the host-frame submission's.  k_gather_rois_encoded does the same for frames in
 // the camera's own encoding (mpe_track_step_batch_setups_device_encoded[_submit]): it decodes the pixels it gathers, so
-// no mono8 copy of the frames is made first.
+// no mono8 copy of the frames is made first.  k_gather_rois_formats serves a submission whose items differ in image
+// format (mpe_track_step_batch_formats[_submit]): stride, image end and encoding per item, from a format table.
 #include "mpe_host.h"
 #include "mpe_gather.h"
 
@@ -53,6 +54,30 @@ __global__ __launch_bounds__(256) void k_gather_rois_encoded(const GatherItem* _
       make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+// The same slots from images that differ in FORMAT: item e is an image of fmts[tab[e].format] (stride, image end, bytes
+// per pixel, channel / byte order), the segment is the one of the two kernels above for that format
+// (gather_segment_format).  Segments are indexed slot after slot, so a wave (64 consecutive segments) holds two slots —
+// and so, at most, two formats — only where one slot ends inside it; the submission places the slots of one format
+// next to each other within every set-up range, so the four-way branch diverges in those boundary waves alone.
+__global__ __launch_bounds__(256) void k_gather_rois_formats(const GatherItem* __restrict__ tab,
+                                                             const GatherFormat* __restrict__ fmts, int n,
+                                                             uint8_t* __restrict__ dst, size_t slot_bytes, int rows,
+                                                             int segs_per_row) {
+  const size_t segs_per_slot = (size_t)rows * segs_per_row;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)n * segs_per_slot) return;
+  const int e = (int)(idx / segs_per_slot);
+  const int rem = (int)(idx - (size_t)e * segs_per_slot);
+  const int r = rem / segs_per_row, seg = rem - r * segs_per_row;
+  const GatherItem it = tab[e];
+  const GatherFormat f = fmts[it.format];
+  uint32_t o[4];
+  gather_segment_format(GatherLoads(), it.img, f, it.x, it.y, it.w, it.h, r, seg, o);
+  // (slot base, pitch and segment offset are multiples of 16)
+  *reinterpret_cast<uint4*>(dst + (size_t)it.slot * slot_bytes + ((size_t)r * segs_per_row + seg) * 16) =
+      make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 }  // namespace
 
 namespace mpe_host {
@@ -91,6 +116,16 @@ hipError_t launch_gather_rois_encoded(const GatherItem* tab, int n, uint8_t* dst
     default:  // (mono8 goes through launch_gather_rois; anything else was refused by the entry)
       return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_rois_formats(const GatherItem* tab, const GatherFormat* fmts, int n, uint8_t* dst, const FrameGeom& g,
+                                      hipStream_t s) {
+  const size_t total = (size_t)n * g.rows * g.segs_per_row;
+  const size_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_gather_rois_formats, dim3((unsigned)blocks), dim3(256), 0, s, tab, fmts, n, dst,
+                     (size_t)g.rows * g.pitch, g.rows, g.segs_per_row);
   return hipGetLastError();
 }
 

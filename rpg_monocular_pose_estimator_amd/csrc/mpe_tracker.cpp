@@ -488,6 +488,10 @@ bool same_camera_markers_params(const mpe_tracker* a, const mpe_tracker* b) {
   return a->markers == b->markers && a->D == b->D && !std::memcmp(a->K, b->K, sizeof(a->K)) &&
          !std::memcmp(&a->p, &b->p, sizeof(mpe_params));
 }
+bool same_image_format(const mpe_image_format& a, const mpe_image_format& b) {
+  return a.rows == b.rows && a.cols == b.cols && a.stride_bytes == b.stride_bytes && a.encoding == b.encoding &&
+         (a.encoding != MPE_ENC_MONO16 || (a.src_big_endian != 0) == (b.src_big_endian != 0));
+}
 bool same_setup(const mpe_tracker* a, const mpe_tracker* b) { return a->h == b->h && same_camera_markers_params(a, b); }
 
 struct BatchCtx {
@@ -513,6 +517,25 @@ struct BatchCtx {
   int big_endian = 0;             // ... their mono16 values are big-endian
   std::vector<mpe_track_setup> setups;
   std::vector<int> lane_setup, item_setup;
+  // lanes that differ in image format (the *_formats entries): lane i's images are of lane_formats[i] — rows, cols,
+  // stride and encoding per lane; formats = the distinct ones, lane_format the index of every lane's among them
+  const mpe_image_format* lane_formats = nullptr;
+  std::vector<mpe_image_format> formats;
+  std::vector<int> lane_format, item_format;
+
+  void set_formats(const mpe_image_format* f) {
+    lane_formats = f;
+    formats.clear();
+    lane_format.assign((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+      size_t k = 0;
+      while (k < formats.size() && !same_image_format(formats[k], f[i])) ++k;
+      if (k == formats.size()) formats.push_back(f[i]);
+      lane_format[(size_t)i] = (int)k;
+    }
+  }
+  int rows_of(int i) const { return lane_formats ? lane_formats[i].rows : rows; }
+  int cols_of(int i) const { return lane_formats ? lane_formats[i].cols : cols; }
 
   int validate(mpe_tracker* const* ts_, int n_, bool mixed_ = false) {
     ts = ts_;
@@ -561,32 +584,36 @@ struct BatchCtx {
       t->t_predicted = times[i];
       if (t->it_since_initialized < 1) {
         t->roi[0] = t->roi[1] = 0;
-        t->roi[2] = cols;
-        t->roi[3] = rows;
+        t->roi[2] = cols_of(i);
+        t->roi[3] = rows_of(i);
         L[(size_t)i].tracking = false;
       } else {
         if (t->it_since_initialized >= 2)
           t->predicted = predict_pose(t->current, t->previous, t->t_current, t->t_previous, t->t_predicted);
         for (int k = 0; k < n_markers(t); ++k)
           project(t, t->predicted, &t->markers[3 * k], t->predicted_px[2 * k], t->predicted_px[2 * k + 1]);
-        determine_roi(t, rows, cols);
+        determine_roi(t, rows_of(i), cols_of(i));
         L[(size_t)i].tracking = true;
       }
       L[(size_t)i].op = OP_DETECT;
     }
   }
 
-  bool is_big(int i) const { return (long long)ts[i]->roi[2] * ts[i]->roi[3] * 4 > (long long)rows * cols; }
+  bool is_big(int i) const { return (long long)ts[i]->roi[2] * ts[i]->roi[3] * 4 > (long long)rows_of(i) * cols_of(i); }
 
   // submit the DETECT lanes of one size class (two classes, so that a few whole-image retries do not inflate every
   // ROI slot of the batch); returns the number of lanes submitted or < 0
-  // the lanes at `op` (of size class `big`; < 0: both) as items of a lock-step submission; pend = those lanes
-  void gather_items(BatchOp op, int big) {
+  // the lanes at `op` (of size class `big`; < 0: both — of format `fmt`; < 0: all) as items of a lock-step submission;
+  // pend = those lanes
+  void gather_items(BatchOp op, int big, int fmt = -1) {
     items.clear();
     item_setup.clear();
+    item_format.clear();
     pend.clear();
     for (int i = 0; i < n; ++i) {
       if (L[(size_t)i].op != op || (big >= 0 && (int)is_big(i) != big)) continue;
+      if (fmt >= 0 && lane_format[(size_t)i] != fmt) continue;
+      if (lane_formats) item_format.push_back(lane_format[(size_t)i]);
       const mpe_tracker* t = ts[i];
       mpe_track_item it;
       it.img = imgs[i];
@@ -604,7 +631,11 @@ struct BatchCtx {
     gather_items(OP_DETECT, big);
     if (items.empty()) return 0;
     // (MPE_ENC_MONO8: the encoded entry hands the call to mpe_track_step_batch_setups_device_submit)
-    const int rc = frames_on_device
+    const int rc = lane_formats
+                       ? mpe_track_step_batch_formats_submit(h, items.data(), item_setup.data(), item_format.data(),
+                                                             (int)items.size(), formats.data(), (int)formats.size(),
+                                                             frames_on_device ? 1 : 0, setups.data(), (int)setups.size())
+                   : frames_on_device
                        ? mpe_track_step_batch_setups_device_encoded_submit(h, items.data(), item_setup.data(), (int)items.size(),
                                                                            rows, cols, stride, encoding, big_endian,
                                                                            setups.data(), (int)setups.size())
@@ -680,8 +711,8 @@ struct BatchCtx {
       }
     } else if (ln.num_loops < 2) {  // too few LEDs in the ROI: search the whole image once
       t->roi[0] = t->roi[1] = 0;
-      t->roi[2] = cols;
-      t->roi[3] = rows;
+      t->roi[2] = cols_of(i);
+      t->roi[3] = rows_of(i);
       ln.op = OP_DETECT;
     } else {
       ln.op = OP_DONE;
@@ -689,17 +720,27 @@ struct BatchCtx {
   }
 
   // all OP_DETECT_WIDE lanes through ONE mpe_track_step_batch_wide (synchronous), advanced as collect_detect advances
-  // the narrow ones
+  // the narrow ones; lanes that differ in image format: one call per distinct format among them
   int detect_wide() {
-    gather_items(OP_DETECT_WIDE, -1);
+    if (!lane_formats) return detect_wide_format(-1);
+    for (size_t f = 0; f < formats.size(); ++f) {
+      const int rc = detect_wide_format((int)f);
+      if (rc != MPE_OK) return rc;
+    }
+    return MPE_OK;
+  }
+  int detect_wide_format(int fmt) {
+    gather_items(OP_DETECT_WIDE, -1, fmt);
     if (items.empty()) return MPE_OK;
     const int m = (int)items.size();
     wdets.resize((size_t)m);
     corr.resize((size_t)m * 2 * MPE_MAX_MARKERS);
     res.resize((size_t)m);
-    const int rc = mpe_track_step_batch_wide(h, items.data(), item_setup.data(), m, rows, cols, stride, frames_on_device ? 1 : 0,
-                                             encoding, big_endian, setups.data(), (int)setups.size(), wdets.data(),
-                                             corr.data(), res.data());
+    const mpe_image_format one = {rows, cols, stride, encoding, big_endian};
+    const mpe_image_format& f = fmt >= 0 ? formats[(size_t)fmt] : one;
+    const int rc = mpe_track_step_batch_wide(h, items.data(), item_setup.data(), m, f.rows, f.cols, f.stride_bytes,
+                                             frames_on_device ? 1 : 0, f.encoding, f.src_big_endian, setups.data(),
+                                             (int)setups.size(), wdets.data(), corr.data(), res.data());
     if (rc != MPE_OK) {
       pend.clear();
       return rc;
@@ -1018,15 +1059,62 @@ int mpe_tracker_estimate_batch_device_encoded(mpe_tracker* const* ts, int n, con
                         src_big_endian ? 1 : 0);
 }
 
+// the formats of the *_formats entries, before a tracker's state is touched: the codes of
+// mpe_track_step_batch_formats_submit
+static int check_formats(mpe_handle* h, const mpe_image_format* formats, int n, bool on_device) {
+  for (int i = 0; i < n; ++i) {
+    const mpe_image_format& f = formats[i];
+    const int bpp = mpe::encoding_bytes_per_pixel(f.encoding);
+    if (!bpp) {
+      mpe_host::set_error(h, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+      return MPE_ERR_UNSUPPORTED;
+    }
+    if (f.rows < 1 || f.cols < 1 || f.stride_bytes < (size_t)f.cols * (size_t)bpp) {
+      mpe_host::set_error(h, "bad argument");
+      return MPE_ERR_ARG;
+    }
+    if (!on_device && f.encoding != MPE_ENC_MONO8) {
+      mpe_host::set_error(h, "host frames are mono8 (the encodings are decoded from device frames)");
+      return MPE_ERR_ARG;
+    }
+  }
+  return MPE_OK;
+}
+
+// trackers whose cameras differ in image format (size, stride, encoding): formats[i] is stream i's
+int mpe_tracker_estimate_batch_formats(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int frames_on_device,
+                                       const mpe_image_format* formats, const double* times, mpe_result* out, int* info,
+                                       int* updated) {
+  if (!ts || n < 0 || !imgs || !formats || !times) return MPE_ERR_ARG;
+  if (n == 0) return 0;
+  for (int i = 0; i < n; ++i)
+    if (!imgs[i]) return MPE_ERR_ARG;
+  BatchCtx c;
+  int rc = c.validate(ts, n, true);
+  if (rc != MPE_OK) return rc;
+  if ((rc = check_formats(c.h, formats, n, frames_on_device != 0)) != MPE_OK) return rc;
+  c.frames_on_device = frames_on_device != 0;
+  c.set_formats(formats);
+  c.begin(imgs, 0, 0, 0, times);
+  if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
+    c.cancel();  // (a submission may still be in flight: leave the handle usable)
+    return rc;
+  }
+  return c.outputs(out, 1, info, 8, updated);
+}
+
 // The lock-step loops of N streams over recorded sequences.  Trackers that live on DIFFERENT handles form groups
 // (one group per handle, each with the same camera / marker / parameter set inside the group); the groups are
 // pipelined against each other: while the device works on step k of one group, the host collects, advances and
 // packs another — the host work of a time step (~3 us per stream) hides behind the device latency (~0.2 ms).
-// (mixed: each group may mix cameras, marker sets and parameters — mpe_tracker_run_sequences_batch_mixed_threads)
+// (mixed: each group may mix cameras, marker sets and parameters — mpe_tracker_run_sequences_batch_mixed_threads;
+//  formats: stream i's images are of formats[i] and its frames frame_strides[i] bytes apart —
+//  mpe_tracker_run_sequences_batch_formats_threads; rows .. frame_stride_bytes and the encoding are then not read)
 static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows, int cols,
                                size_t stride_bytes, size_t frame_stride_bytes, const double* times, mpe_result* out,
                                int* info, int n_threads, bool mixed, bool on_device = false, int encoding = MPE_ENC_MONO8,
-                               int big_endian = 0) {
+                               int big_endian = 0, const mpe_image_format* formats = nullptr,
+                               const size_t* frame_strides = nullptr) {
   if (!ts || n < 0 || !frames || !times || n_frames < 0 || n_threads < 1) return MPE_ERR_ARG;
   if (n == 0 || n_frames == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -1048,6 +1136,7 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
   std::vector<std::vector<mpe_tracker*> > gts(G);
   std::vector<std::vector<const uint8_t*> > gimgs(G);
   std::vector<std::vector<double> > gtimes(G);
+  std::vector<std::vector<mpe_image_format> > gformats(G);
   for (size_t g = 0; g < G; ++g) {
     for (int i : members[g]) gts[g].push_back(ts[i]);
     gimgs[g].resize(members[g].size());
@@ -1059,9 +1148,14 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
     ctx[g].big_endian = big_endian;
   }
   for (size_t g = 0; g < G; ++g) {
-    const int rc = check_encoding(hs[g], encoding, cols, stride_bytes);
+    if (formats)
+      for (int i : members[g]) gformats[g].push_back(formats[i]);
+    const int rc = formats ? check_formats(hs[g], gformats[g].data(), (int)gformats[g].size(), on_device)
+                           : check_encoding(hs[g], encoding, cols, stride_bytes);
     if (rc != MPE_OK) return rc;
   }
+  if (formats)
+    for (size_t g = 0; g < G; ++g) ctx[g].set_formats(gformats[g].data());
   // The groups gs[0..) on the calling thread, pipelined against each other: while the device works on step k of one
   // group, the host collects, advances and packs another.  Groups share nothing (own handle, own trackers, own rows
   // of out / info), so disjoint sets of groups can also run on different host threads.
@@ -1087,7 +1181,7 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
           if (rc != MPE_OK) return rc;
         }
         for (size_t k = 0; k < members[g].size(); ++k) {
-          gimgs[g][k] = frames[members[g][k]] + (size_t)f * frame_stride_bytes;
+          gimgs[g][k] = frames[members[g][k]] + (size_t)f * (frame_strides ? frame_strides[members[g][k]] : frame_stride_bytes);
           gtimes[g][k] = times[f];
         }
         ctx[g].begin(gimgs[g].data(), rows, cols, stride_bytes, gtimes[g].data());
@@ -1159,6 +1253,16 @@ int mpe_tracker_run_sequences_batch_device_encoded_threads(mpe_tracker* const* t
                                                            const double* times, mpe_result* out, int* info, int n_threads) {
   return run_sequences_batch(ts, n, d_frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
                              n_threads, true, true, encoding, src_big_endian ? 1 : 0);
+}
+
+// ... every stream in an image format of its own
+int mpe_tracker_run_sequences_batch_formats_threads(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames,
+                                                    int frames_on_device, const mpe_image_format* formats,
+                                                    const size_t* frame_stride_bytes, const double* times, mpe_result* out,
+                                                    int* info, int n_threads) {
+  if (!formats || !frame_stride_bytes) return MPE_ERR_ARG;
+  return run_sequences_batch(ts, n, frames, n_frames, 0, 0, 0, 0, times, out, info, n_threads, true, frames_on_device != 0,
+                             MPE_ENC_MONO8, 0, formats, frame_stride_bytes);
 }
 
 int mpe_tracker_run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows,
