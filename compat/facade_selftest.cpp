@@ -9,6 +9,9 @@
 //   facade_selftest framepath < encoding names
 //       which of the node's three frame paths (in place / back-end decode / cv_bridge) each encoding takes, in the
 //       default build and in the MPE_OPENCV_GRAY_14BIT build (host only)
+//   facade_selftest framepath-sensor < encoding names
+//       the same with the opt-in argument: "<encoding>" and, for each of the opt-ins none, FRAME_OPT_YUV422,
+//       FRAME_OPT_BAYER_SCALAR and both, "<path> <enc>" of the default build (host only)
 //   facade_selftest wide --markers <yaml> --camera "fx fy cx cy" [--dist "k1 k2 p1 p2 k3"] [--points <file> --tol t]
 //                        [--frame <file.raw> --rows R --cols C --frame-tol t]
 //       setWideFrames off and on: setImagePoints + initialise + optimiseAndUpdatePose on a point set of 65 .. 256 points,
@@ -185,6 +188,19 @@ int main(int argc, char** argv) {
       const FramePath p0 = framePathForEncoding(name, false, &e0);
       const FramePath p1 = framePathForEncoding(name, true, &e1);
       std::printf("%s %d %d %d %d\n", name, (int)p0, e0, (int)p1, e1);
+    }
+    return 0;
+  }
+  if (argc >= 2 && !std::strcmp(argv[1], "framepath-sensor")) {  // "<encoding>" + "<path> <enc>" for opt-in 0, 1, 2, 3
+    char name[64];
+    while (std::scanf("%63s", name) == 1) {
+      std::printf("%s", name);
+      for (unsigned opt = 0; opt < 4; ++opt) {
+        int e = 99;
+        const FramePath p = framePathForEncoding(name, false, &e, opt);
+        std::printf(" %d %d", (int)p, e);
+      }
+      std::printf("\n");
     }
     return 0;
   }

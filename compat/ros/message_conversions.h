@@ -83,10 +83,36 @@ inline int mpeEncodingFromString(const std::string& encoding) {
 //! (`gray_14bit`), otherwise they go through cv_bridge like everything the back-end does not know (Bayer ...).
 //! `enc` receives the MPE_ENC_* code for FRAME_BACKEND_DECODE and -1 otherwise: MPE_ENC_MONO8 is 0, so "no code"
 //! must never be spelled 0 (`enc = 0` sent interleaved colour bytes down the mono8 branch).
+//!
+//! `sensor_optin` (defaulted: the two-argument behaviour is unchanged, Bayer and YUV go through cv_bridge) lets the
+//! back-end decode the sensor encodings as well: FRAME_OPT_YUV422 for "yuv422" / "yuv422_yuy2" (the Y byte: exact and
+//! the same in every OpenCV), FRAME_OPT_BAYER_SCALAR for "bayer_rggb8" / "bayer_bggr8" / "bayer_gbrg8" /
+//! "bayer_grbg8" (OpenCV's SCALAR Bayer2Gray rule, see include/mpe.h: an OpenCV that takes its SIMD path can differ by
+//! one gray level, so this is for users who accept the scalar rule).
 enum FramePath { FRAME_IN_PLACE = 0, FRAME_BACKEND_DECODE = 1, FRAME_CV_BRIDGE = 2 };
-inline FramePath framePathForEncoding(const std::string& encoding, bool gray_14bit, int* enc) {
+enum FrameOptIn { FRAME_OPT_NONE = 0, FRAME_OPT_YUV422 = 1, FRAME_OPT_BAYER_SCALAR = 2 };
+// sensor_msgs/Image.encoding -> MPE_ENC_* for the sensor encodings (kept apart from mpeEncodingFromString: whoever
+// switches on that function's result keeps sending these to cv_bridge); -1 for anything else
+inline int mpeSensorEncodingFromString(const std::string& encoding) {
+  if (encoding == "bayer_rggb8") return MPE_ENC_BAYER_RGGB8;
+  if (encoding == "bayer_bggr8") return MPE_ENC_BAYER_BGGR8;
+  if (encoding == "bayer_gbrg8") return MPE_ENC_BAYER_GBRG8;
+  if (encoding == "bayer_grbg8") return MPE_ENC_BAYER_GRBG8;
+  if (encoding == "yuv422") return MPE_ENC_YUV422;
+  if (encoding == "yuv422_yuy2") return MPE_ENC_YUV422_YUY2;
+  return -1;
+}
+inline FramePath framePathForEncoding(const std::string& encoding, bool gray_14bit, int* enc, unsigned sensor_optin = 0) {
   const int e = mpeEncodingFromString(encoding);
   *enc = -1;
+  if (sensor_optin && e < 0) {
+    const int se = mpeSensorEncodingFromString(encoding);
+    const bool yuv = se == MPE_ENC_YUV422 || se == MPE_ENC_YUV422_YUY2;
+    if (se >= 0 && (sensor_optin & (yuv ? FRAME_OPT_YUV422 : FRAME_OPT_BAYER_SCALAR))) {
+      *enc = se;
+      return FRAME_BACKEND_DECODE;
+    }
+  }
   if (e == MPE_ENC_MONO8) return FRAME_IN_PLACE;
   if (e == MPE_ENC_MONO16 || (gray_14bit && e > 0)) {
     *enc = e;

@@ -104,12 +104,22 @@ class MPENode {
     // says that the linked OpenCV converts 8-bit RGB to gray with the 14-bit weights (OpenCV <= 3.4.1: 1868 / 9617 /
     // 4899, >> 14 — the rule mpe_convert_to_mono8 restates, for the OpenCV 3.3 of the reference's platform); OpenCV
     // >= 3.4.2 uses 15-bit weights and can differ by one gray level, which near threshold_value flips LED pixels.
+    // The sensor encodings are decoded by the back-end on request: -DMPE_BACKEND_YUV422 for yuv422 / yuv422_yuy2 (the Y
+    // byte: exact, safe with any OpenCV), -DMPE_OPENCV_BAYER_SCALAR for the 8-bit Bayer patterns (OpenCV's scalar
+    // Bayer2Gray rule; its SIMD path can differ by one gray level).
     cv_bridge::CvImageConstPtr mono;
     int enc = -1;
+    unsigned optin = FRAME_OPT_NONE;
+#ifdef MPE_BACKEND_YUV422
+    optin |= FRAME_OPT_YUV422;
+#endif
+#ifdef MPE_OPENCV_BAYER_SCALAR
+    optin |= FRAME_OPT_BAYER_SCALAR;
+#endif
 #ifdef MPE_OPENCV_GRAY_14BIT
-    const FramePath path = framePathForEncoding(msg->encoding, true, &enc);
+    const FramePath path = framePathForEncoding(msg->encoding, true, &enc, optin);
 #else
-    const FramePath path = framePathForEncoding(msg->encoding, false, &enc);
+    const FramePath path = framePathForEncoding(msg->encoding, false, &enc, optin);
 #endif
     const uint8_t* pixels = nullptr;
     size_t step = 0;

@@ -165,13 +165,39 @@ int mpe_estimate_batch(mpe_handle* h, const uint8_t* frames, int n_frames, int r
  *   MPE_ENC_MONO16: cv::Mat::convertTo(CV_8U, 255. / 65535.) = saturate_cast<uchar>((float)v * (float)(255. / 65535.)),
  *       after cv_bridge's byte swap when Image.is_bigendian differs from the host (src_big_endian)
  *   MPE_ENC_MONO8: a (strided) copy.
- * Bayer encodings (cv_bridge demosaics them through COLOR_Bayer*2GRAY) are not covered: MPE_ERR_UNSUPPORTED. */
+ *   MPE_ENC_YUV422 (U Y V Y) / MPE_ENC_YUV422_YUY2 (Y U Y V), two source bytes per pixel: cvtColor(...,
+ *       COLOR_YUV2GRAY_UYVY / _YUY2) — the gray value is the pixel's Y byte (byte 1 of its pair / byte 0), an exact copy
+ *       in every OpenCV.  Odd cols are legal.
+ *   MPE_ENC_BAYER_RGGB8 / BGGR8 / GBRG8 / GRBG8, one source byte per pixel; the name gives the colours of the image
+ *       pixels (0,0), (0,1), (1,0), (1,1): cvtColor(..., COLOR_Bayer{BG,RG,GR,GB}2GRAY), OpenCV's SCALAR Bayer2Gray with
+ *       the 14-bit weights R 4899, G 9617, B 1868, every neighbour weighted by the weight of its own colour:
+ *         red or blue site, centre c of colour X, the four diagonal neighbours of the other colour Z:
+ *           Y = (wZ * (four diagonal neighbours) + 9617 * (four edge neighbours) + 4 * wX * c + 2^15) >> 16
+ *         green site, wV / wH the weights of the colours above-below / left-right:
+ *           Y = (wV * (up + down) + wH * (left + right) + 2 * 9617 * c + 2^14) >> 15
+ *       Only interior pixels are computed: output pixel (r, c) is the value at (clamp(r, 1, rows - 2),
+ *       clamp(c, 1, cols - 2)), so the border rows and columns repeat their inner neighbours, as OpenCV's do; an image
+ *       with rows < 3 or cols < 3 decodes to all zeros.  This is a restatement nothing reference-held pins (the
+ *       reference calls cv_bridge::toCvCopy(..., MONO8) and was never run on Bayer frames here), and OpenCV's SIMD
+ *       path for this conversion rounds per term and can differ from its scalar path by one gray level: a caller who
+ *       needs the linked OpenCV's bytes keeps cv_bridge for Bayer frames (compat/ros/mpe_ros_glue.cpp does, unless
+ *       built with -DMPE_OPENCV_BAYER_SCALAR).
+ * 16-bit Bayer and every code outside {0 .. 5, 16 .. 21}: MPE_ERR_UNSUPPORTED.  The entries that take HOST frames beside
+ * an encoding (mpe_track_step_batch_wide, the *_formats entries) decode device frames alone: host frames in a Bayer or
+ * YUV encoding are MPE_ERR_UNSUPPORTED there (what these codes answered before they existed), in one of the other five
+ * non-mono8 encodings MPE_ERR_ARG as ever. */
 #define MPE_ENC_MONO8 0
 #define MPE_ENC_BGR8 1
 #define MPE_ENC_RGB8 2
 #define MPE_ENC_BGRA8 3
 #define MPE_ENC_RGBA8 4
 #define MPE_ENC_MONO16 5
+#define MPE_ENC_BAYER_RGGB8 16 /* sensor_msgs "bayer_rggb8" -> cv::COLOR_BayerBG2GRAY */
+#define MPE_ENC_BAYER_BGGR8 17 /* "bayer_bggr8" -> COLOR_BayerRG2GRAY */
+#define MPE_ENC_BAYER_GBRG8 18 /* "bayer_gbrg8" -> COLOR_BayerGR2GRAY */
+#define MPE_ENC_BAYER_GRBG8 19 /* "bayer_grbg8" -> COLOR_BayerGB2GRAY */
+#define MPE_ENC_YUV422 20      /* "yuv422" = U Y V Y  -> COLOR_YUV2GRAY_UYVY */
+#define MPE_ENC_YUV422_YUY2 21 /* "yuv422_yuy2" = Y U Y V -> COLOR_YUV2GRAY_YUY2 */
 int mpe_convert_to_mono8(mpe_handle* h, const void* src, int src_on_device, int encoding, int src_big_endian, int n_frames,
                          int rows, int cols, size_t src_stride_bytes, size_t src_frame_stride_bytes, uint8_t* dst,
                          int dst_on_device);
@@ -406,7 +432,7 @@ int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_ite
  * serve this submit too; ordering as above.  Usage errors, all before any device work: whatever
  * mpe_track_step_batch_setups_device_submit refuses (every img must lie, with its whole ENCODED image —
  * (rows - 1) * stride_bytes + cols * bytes per pixel —, inside one device allocation on the handle's device);
- * stride_bytes < cols * bytes per pixel: MPE_ERR_ARG; an encoding outside the six (Bayer, YUV): MPE_ERR_UNSUPPORTED, as
+ * stride_bytes < cols * bytes per pixel: MPE_ERR_ARG; an encoding outside MPE_ENC_* (16-bit Bayer, ...): MPE_ERR_UNSUPPORTED, as
  * mpe_convert_to_mono8 answers it. */
 int mpe_track_step_batch_setups_device_encoded(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
                                                int rows, int cols, size_t stride_bytes, int encoding, int src_big_endian,
@@ -435,7 +461,7 @@ int mpe_track_step_batch_setups_device_encoded_submit(mpe_handle* h, const mpe_t
  * (one that fits the largest image of the call but not the item's never reaches the gather); frames_on_device 1 and an
  * img that does not lie, with its OWN encoded image — (rows - 1) * stride_bytes + cols * bytes per pixel —, inside one
  * device allocation on the handle's device (host memory, pinned included); a submission that is not yet collected.
- * MPE_ERR_UNSUPPORTED: an encoding outside the six.  n == 0: MPE_OK, nothing submitted. */
+ * MPE_ERR_UNSUPPORTED: an encoding outside MPE_ENC_*.  n == 0: MPE_OK, nothing submitted. */
 typedef struct mpe_image_format {
   int rows, cols;      /* pixels */
   size_t stride_bytes; /* SOURCE bytes per row (Image.step) */
@@ -646,7 +672,7 @@ int mpe_tracker_run_sequences_batch_device_threads(mpe_tracker* const* trackers,
  * for MPE_ENC_MONO16; stride_bytes and frame_stride_bytes in SOURCE bytes, rows and cols in pixels): the detections go
  * through mpe_track_step_batch_setups_device_encoded_submit, the whole-image ones (a cold first step, a retry) as well —
  * the gather then decodes the whole frame.  Records and info are byte-identical to those of the entries above over
- * the same frames after mpe_convert_to_mono8.  An encoding outside the six is MPE_ERR_UNSUPPORTED, a stride below
+ * the same frames after mpe_convert_to_mono8.  An encoding outside MPE_ENC_* is MPE_ERR_UNSUPPORTED, a stride below
  * cols * bytes per pixel MPE_ERR_ARG, both before any tracker is touched. */
 int mpe_tracker_estimate_batch_device_encoded(mpe_tracker* const* trackers, int n, const uint8_t* const* d_imgs, int rows,
                                               int cols, size_t stride_bytes, int encoding, int src_big_endian,
@@ -667,7 +693,7 @@ int mpe_tracker_run_sequences_batch_device_encoded_threads(mpe_tracker* const* t
  * among those streams, the re-initialisations through the brute-force entries as before (they work on detections).
  * Results are identical to mpe_tracker_estimate per stream and to the entries above over each format's trackers alone.
  * A null pointer, a bad format (rows, cols, stride) or an encoded format with host frames is MPE_ERR_ARG, an encoding
- * outside the six MPE_ERR_UNSUPPORTED, all before any tracker is touched. */
+ * outside MPE_ENC_* MPE_ERR_UNSUPPORTED, all before any tracker is touched. */
 int mpe_tracker_estimate_batch_formats(mpe_tracker* const* trackers, int n, const uint8_t* const* imgs, int frames_on_device,
                                        const mpe_image_format* formats, const double* times, mpe_result* out, int* info,
                                        int* updated);

@@ -331,16 +331,16 @@ def tracker_run_sequences_batch_mixed(trackers, frames, times, threads=1):
 
 def _device_images(imgs, lead, encoding="mono8"):
     """The streams' images in device memory: a list of torch CUDA tensors, one per stream, or one tensor with a leading
-    stream dimension; `lead` dimensions in front of the image.  mono8: (rows, cols) uint8.  Any other encoding
-    (ENCODINGS): (rows, cols, bytes per pixel) uint8 with the bytes of a pixel contiguous, or, mono16, (rows, cols)
-    uint16 / int16.  All on one device, pixels contiguous within a row, the same strides; row stride and storage offset
+    stream dimension; `lead` dimensions in front of the image.  mono8 and the Bayer patterns: (rows, cols) uint8.  Any
+    other encoding (ENCODINGS): (rows, cols, bytes per pixel) uint8 with the bytes of a pixel contiguous (YUV 4:2:2: 2),
+    or, mono16, (rows, cols) uint16 / int16.  All on one device, pixels contiguous within a row, the same strides; row stride and storage offset
     are free.  Work queued on torch's current stream of that device is waited for (the frames must be final when they
     are submitted).  -> (the tensors — keep them alive across the call —, device pointers, the lead + (rows, cols)
     shape, their strides in BYTES)."""
     import torch
     if encoding not in ENCODINGS:
         raise MpeError("encoding %r: one of %s" % (encoding, ", ".join(sorted(ENCODINGS))))
-    bpp = {"mono8": 1, "mono16": 2, "bgr8": 3, "rgb8": 3}.get(encoding, 4)
+    bpp = ENCODING_BPP[encoding]
     ts = list(imgs.unbind(0)) if _is_torch(imgs) else list(imgs)
     t0 = ts[0]
     for t in ts:
@@ -350,9 +350,9 @@ def _device_images(imgs, lead, encoding="mono8"):
         elif ok and t.dtype == torch.uint8:    # the bytes of a pixel as a last dimension
             ok = t.dim() == lead + 3 and t.shape[-1] == bpp and t.stride(-1) == 1 and t.stride(-2) == bpp
         elif ok:
-            ok = bpp == 2 and t.dtype in (torch.uint16, torch.int16) and t.dim() == lead + 2 and t.stride(-1) == 1
+            ok = encoding == "mono16" and t.dtype in (torch.uint16, torch.int16) and t.dim() == lead + 2 and t.stride(-1) == 1
         if not ok:
-            raise MpeError("device frames: torch CUDA tensors with contiguous rows are needed — (rows, cols) uint8 for mono8, "
+            raise MpeError("device frames: torch CUDA tensors with contiguous rows are needed — (rows, cols) uint8 for mono8 / Bayer, "
                            "(rows, cols, bytes per pixel) uint8 or, mono16, (rows, cols) uint16 / int16 for the other "
                            "encodings (host frames: the host entries)")
         if t.shape != t0.shape or t.stride() != t0.stride() or t.device != t0.device or t.dtype != t0.dtype:
@@ -411,7 +411,7 @@ class ImageFormat(C.Structure):  # mpe_image_format
 def _image_format(img, lead, spec):
     """One image (lead 0) or sequence (lead 1: frames in front) of a *_formats entry: a numpy array (host) or a torch
     CUDA tensor (device).  spec: an ImageFormat, taken as it is; or an encoding name / (name, big_endian) / None
-    ("mono8"), and the format is read off the array — (rows, cols) uint8 for mono8, (rows, cols, bytes per pixel) uint8
+    ("mono8"), and the format is read off the array — (rows, cols) uint8 for mono8 / Bayer, (rows, cols, bytes per pixel) uint8
     or, mono16, (rows, cols) uint16 / int16 for the other encodings, pixels contiguous within a row.
     -> (ImageFormat, address, frame stride in bytes (lead 1, else 0))."""
     dev = _is_torch(img)
@@ -425,14 +425,14 @@ def _image_format(img, lead, spec):
     name = name or "mono8"
     if name not in ENCODINGS:
         raise MpeError("encoding %r: one of %s" % (name, ", ".join(sorted(ENCODINGS))))
-    bpp = {"mono8": 1, "mono16": 2, "bgr8": 3, "rgb8": 3}.get(name, 4)
+    bpp = ENCODING_BPP[name]
     shape, nd = tuple(img.shape), len(img.shape)
     if es == 1 and bpp > 1:
         ok = nd == lead + 3 and shape[-1] == bpp and strides[-1] == 1 and strides[-2] == bpp
     else:
-        ok = es == min(bpp, 2) and bpp <= 2 and nd == lead + 2 and strides[-1] == es
+        ok = es == bpp and (es == 1 or name == "mono16") and nd == lead + 2 and strides[-1] == es
     if not ok:
-        raise MpeError("%s frames: (rows, cols) uint8 for mono8, (rows, cols, bytes per pixel) uint8 or, mono16, (rows, cols) "
+        raise MpeError("%s frames: (rows, cols) uint8 for mono8 / Bayer, (rows, cols, bytes per pixel) uint8 or, mono16, (rows, cols) "
                        "uint16 / int16 for the other encodings, pixels contiguous within a row" % name)
     return (ImageFormat(int(shape[lead]), int(shape[lead + 1]), int(strides[lead]), ENCODINGS[name], int(bool(big))), ptr,
             fstride)
@@ -667,7 +667,12 @@ def find_correspondences(pred_px, det, tol):
     return corr[:n].copy()
 
 
-ENCODINGS = {"mono8": 0, "bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4, "mono16": 5}  # MPE_ENC_*
+ENCODINGS = {"mono8": 0, "bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4, "mono16": 5,  # MPE_ENC_*
+             "bayer_rggb8": 16, "bayer_bggr8": 17, "bayer_gbrg8": 18, "bayer_grbg8": 19, "yuv422": 20, "yuv422_yuy2": 21}
+# source bytes per pixel.  Frames are (rows, cols) uint8 for 1 (mono8, Bayer), (rows, cols, bytes per pixel) uint8 for
+# the others (YUV 4:2:2: the pixel's two bytes), or, mono16 alone, (rows, cols) uint16 / int16
+ENCODING_BPP = {"mono8": 1, "bgr8": 3, "rgb8": 3, "bgra8": 4, "rgba8": 4, "mono16": 2, "bayer_rggb8": 1, "bayer_bggr8": 1,
+                "bayer_gbrg8": 1, "bayer_grbg8": 1, "yuv422": 2, "yuv422_yuy2": 2}
 
 
 def demo_params(**kw):
@@ -1125,18 +1130,26 @@ class Handle:
 
     def convert_to_mono8(self, src, encoding, big_endian=False):
         """mpe_convert_to_mono8 for a batch: src (n, rows, cols[, channels]) uint8 / (n, rows, cols) uint16 numpy array
-        (host) or torch CUDA tensor; encoding "mono8" | "bgr8" | "rgb8" | "bgra8" | "rgba8" | "mono16".
+        (host) or torch CUDA tensor; encoding: one of ENCODINGS — (n, rows, cols) uint8 for mono8 and the Bayer patterns,
+        (n, rows, cols, 2) uint8 for yuv422 / yuv422_yuy2.  A device source whose pixels are contiguous within a row is
+        read in place, whatever its row stride, frame stride and storage offset are.
         -> (n, rows, cols) uint8, numpy for a host source, a torch CUDA tensor for a device source."""
         enc = ENCODINGS[encoding]
         if _is_torch(src):
             import torch
-            src = src.contiguous()
             n, rows, cols = src.shape[:3]
-            bpp = src.element_size() * (src.shape[3] if src.dim() == 4 else 1)
+            es = src.element_size()
+            bpp = es * (src.shape[3] if src.dim() == 4 else 1)
+            dense = src.stride(-1) == 1 and (src.dim() == 3 or src.stride(2) == src.shape[3])
+            # (the stride of a dimension of size 1 says nothing)
+            stride = src.stride(1) * es if rows > 1 else cols * bpp
+            fstride = src.stride(0) * es if n > 1 else rows * stride
+            if not (dense and stride >= cols * bpp and fstride >= rows * stride):
+                src = src.contiguous()
+                stride, fstride = cols * bpp, rows * cols * bpp
             dst = torch.empty((n, rows, cols), dtype=torch.uint8, device=src.device)
             rc = self._lib.mpe_convert_to_mono8(self._h, C.c_void_p(src.data_ptr()), 1, enc, int(bool(big_endian)), n, rows,
-                                                cols, C.c_size_t(cols * bpp), C.c_size_t(rows * cols * bpp),
-                                                C.c_void_p(dst.data_ptr()), 1)
+                                                cols, C.c_size_t(stride), C.c_size_t(fstride), C.c_void_p(dst.data_ptr()), 1)
             self._check(rc, "mpe_convert_to_mono8")
             self.synchronize()
             return dst

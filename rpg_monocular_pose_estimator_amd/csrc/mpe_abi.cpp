@@ -3,6 +3,7 @@
 // refinement, primitive batches, the batch entries (host, device-resident, streaming), frame decode, pinned memory,
 // several GPUs from one process (threads; RCCL record gather).
 #include "mpe_host.h"
+#include "mpe_pixel.h"  // (encoding_bytes_per_pixel)
 
 namespace {
 template <class Fn>
@@ -529,9 +530,8 @@ int mpe_convert_to_mono8(mpe_handle* h, const void* src, int src_on_device, int 
                          int rows, int cols, size_t src_stride_bytes, size_t src_frame_stride_bytes, uint8_t* dst,
                          int dst_on_device) {
   if (!h || !src || !dst || n_frames < 0 || rows <= 0 || cols <= 0) return fail(h, MPE_ERR_ARG, "bad argument");
-  if (encoding < MPE_ENC_MONO8 || encoding > MPE_ENC_MONO16)
-    return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
-  const size_t bpp = encoding == MPE_ENC_MONO8 ? 1 : (encoding == MPE_ENC_MONO16 ? 2 : ((encoding == MPE_ENC_BGRA8 || encoding == MPE_ENC_RGBA8) ? 4 : 3));
+  const size_t bpp = (size_t)mpe::encoding_bytes_per_pixel(encoding);
+  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)");
   if (src_stride_bytes < bpp * (size_t)cols || src_frame_stride_bytes < src_stride_bytes * (size_t)rows)
     return fail(h, MPE_ERR_ARG, "source strides smaller than the image");
   if (n_frames == 0) return MPE_OK;

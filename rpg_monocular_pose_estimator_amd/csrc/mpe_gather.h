@@ -13,9 +13,14 @@
 // each by the rules of mpe_pixel.h — the bytes mpe_convert_to_mono8 would have written into a mono8 copy of the frame.
 // x, y, w, h stay in pixels; stride and img_bytes are source bytes.
 //
+// gather_segment_yuv is the 2-byte segment with byte selection in place of mono16_px (yuv422 / yuv422_yuy2).
+// gather_segment_bayer is the first NEIGHBOURHOOD decode: the 16 pixels of a slot row come from the 3 x 3 surroundings
+// of their (clamped, see bayer_site) sites, three image rows of 18 source bytes, which cross the ROI's edge but never
+// the image's.  Both keep every property stated above.
+//
 // gather_segment_format is the segment of a submission whose items differ in image format (k_gather_rois_formats):
 // stride, image end, bytes per pixel and channel / byte order come from the item's entry of a format table, and the
-// segment is the one of the two functions above that the entry names.  Every property stated above holds per item,
+// segment is the one of the functions above that the entry names.  Every property stated above holds per item,
 // against the item's OWN image end.
 #pragma once
 #include <stddef.h>
@@ -45,10 +50,10 @@ static_assert(sizeof(GatherItem) == 32, "table entries of 32 bytes");
 struct GatherFormat {
   uint64_t stride;     // source bytes per row
   uint64_t img_bytes;  // the image ends with the last pixel of its last row: (rows - 1) * stride + cols * bpp
-  int bpp;             // source bytes per pixel: 1 mono8, 2 mono16, 3 bgr8 / rgb8, 4 bgra8 / rgba8
-  int rgb;             // colour pixels are R G B [A] (else B G R [A])
-  int big_endian;      // the mono16 values are
-  int pad_;
+  int bpp;             // source bytes per pixel: 1 mono8 / Bayer, 2 mono16 / YUV, 3 bgr8 / rgb8, 4 bgra8 / rgba8
+  int rgb;             // colour pixels are R G B [A] (else B G R [A]); Bayer: the image's cols
+  int big_endian;      // the mono16 values are; YUV: the Y byte is byte 1 of the pixel's two; Bayer: the image's rows
+  int kind;            // 0 (or PIX_PLAIN): bpp names the decode; PIX_YUV; PIX_BAYER | bayer_phase << 8
 };
 static_assert(sizeof(GatherFormat) == 32, "table entries of 32 bytes");
 
@@ -103,8 +108,9 @@ __host__ __device__ inline void gather_segment(const Loads& mem, const uint8_t* 
 
 // pixels [16 * seg, 16 * seg + 16) of slot row r, decoded from BPP source bytes each -> out[0..3] (little endian).
 // img_bytes: the image ends with the last pixel of its last row, (rows - 1) * stride + cols * BPP.  rgb: the colour
-// pixels are R G B [A] (else B G R [A]); big_endian: the mono16 values are (BPP 2 alone reads it).
-template <int BPP, class Loads>
+// pixels are R G B [A] (else B G R [A]); big_endian: the mono16 values are (BPP 2 alone reads it).  YUV (BPP 2): the
+// pixel is the Y byte of its two source bytes, byte 1 when big_endian (yuv422) and byte 0 otherwise (yuv422_yuy2).
+template <int BPP, class Loads, bool YUV = false>
 __host__ __device__ inline void gather_segment_encoded(const Loads& mem, const uint8_t* img, size_t img_bytes, size_t stride,
                                                        int x, int y, int w, int h, int r, int seg, bool rgb, bool big_endian,
                                                        uint32_t out[4]) {
@@ -138,7 +144,14 @@ __host__ __device__ inline void gather_segment_encoded(const Loads& mem, const u
 #pragma unroll
   for (int i = 0; i < ND; ++i) s[i] = (uint32_t)(((((uint64_t)d[i + 1]) << 32) | d[i]) >> (8 * sh));
   unsigned px[16];
-  if constexpr (BPP == 2) {
+  if constexpr (BPP == 2 && YUV) {
+    const unsigned ysh = big_endian ? 8u : 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      px[2 * k] = (s[k] >> ysh) & 0xFFu;
+      px[2 * k + 1] = (s[k] >> (16u + ysh)) & 0xFFu;
+    }
+  } else if constexpr (BPP == 2) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       unsigned a = s[k] & 0xFFFFu, b = s[k] >> 16;
@@ -172,11 +185,109 @@ __host__ __device__ inline void gather_segment_encoded(const Loads& mem, const u
   }
 }
 
-// the same 16 slot bytes from an image of format f: the segment function f names
+// pixels [16 * seg, 16 * seg + 16) of slot row r from a YUV 4:2:2 image: the Y byte of every pixel's two source bytes,
+// byte y_byte (yuv_y_byte).  img_bytes = (rows - 1) * stride + cols * 2.
 template <class Loads>
+__host__ __device__ inline void gather_segment_yuv(const Loads& mem, const uint8_t* img, size_t img_bytes, size_t stride, int x,
+                                                   int y, int w, int h, int r, int seg, int y_byte, uint32_t out[4]) {
+  gather_segment_encoded<2, Loads, true>(mem, img, img_bytes, stride, x, y, w, h, r, seg, false, y_byte != 0, out);
+}
+
+// pixels [16 * seg, 16 * seg + 16) of slot row r from a Bayer image of rows x cols pixels (img_bytes = (rows - 1) *
+// stride + cols), decoded by bayer_px.  Output pixel (Y, X) = (y + r, x + c) takes the value of the interior site
+// (bayer_site(Y, rows), bayer_site(X, cols)), whose colour comes from its IMAGE coordinates.  The sites of the 16 pixels
+// are consecutive columns from cxa = bayer_site(x + 16 * seg, cols) on; their surroundings are the source columns
+// cxa - 1 .. cxa + 16 of the image rows cy - 1, cy, cy + 1: three times up to six aligned dwords, of which only those
+// are loaded that hold a column the segment needs, all of them inside their image row (1 <= cxa, last site <= cols - 2).
+// The values v[j] of the sites cxa + j are then put where the clamp sends them: pixel k is v[k], or v[k - 1] behind
+// image column 0 (whose site is column 1), and the image's last column repeats the pixel in front of it.
+template <class Loads>
+__host__ __device__ inline void gather_segment_bayer(const Loads& mem, const uint8_t* img, size_t img_bytes, size_t stride,
+                                                     int rows, int cols, int x, int y, int w, int h, int r, int seg,
+                                                     int phase, uint32_t out[4]) {
+  out[0] = out[1] = out[2] = out[3] = 0;
+  const int c0 = 16 * seg;
+  if (r >= h || c0 >= w || rows < 3 || cols < 3) return;  // (an image below 3 x 3 decodes to zeros)
+  const int n = w - c0 < 16 ? w - c0 : 16;                // pixels wanted
+  const int X0 = x + c0;                                  // image column of pixel 0
+  const int cy = bayer_site(y + r, rows), cxa = bayer_site(X0, cols);
+  const int cxb = bayer_site(X0 + n - 1, cols);           // the last site: source columns cxa - 1 .. cxb + 1 are wanted
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(img), hi = lo + img_bytes;
+  uint32_t up[5], mid[5], dn[5];  // 18 source bytes from column cxa - 1 on, of the rows cy - 1, cy, cy + 1
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const uintptr_t src = lo + (size_t)(cy - 1 + q) * stride + (size_t)(cxa - 1), end = src + (size_t)(cxb - cxa + 3);
+    const unsigned sh = (unsigned)(src & 3);
+    const uintptr_t base = src - sh;  // aligned; up to 3 bytes in front of src (and of the image)
+    uint32_t d[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const uintptr_t a = base + 4 * (uintptr_t)j;
+      uint32_t v = 0;
+      if (a < end) {
+        if (a >= lo && a + 4 <= hi) {
+          v = mem.ld32(a);
+        } else {  // the dword straddles an end of the image: the wanted bytes of it, one by one
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            if (a + b >= src && a + b < end) v |= mem.ld8(a + b) << (8 * b);
+        }
+      }
+      d[j] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      const uint32_t v = (uint32_t)(((((uint64_t)d[i + 1]) << 32) | d[i]) >> (8 * sh));
+      if (q == 0) up[i] = v;
+      else if (q == 1) mid[i] = v;
+      else dn[i] = v;
+    }
+  }
+  unsigned vs[18], ms[18];  // per source column: up + down, and the middle row
+#pragma unroll
+  for (int i = 0; i < 18; ++i) {
+    const unsigned b = 8u * (unsigned)(i & 3);
+    vs[i] = ((up[i >> 2] >> b) & 0xFFu) + ((dn[i >> 2] >> b) & 0xFFu);
+    ms[i] = (mid[i >> 2] >> b) & 0xFFu;
+  }
+  unsigned v[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) v[j] = bayer_px(vs[j] + vs[j + 2], vs[j + 1], ms[j] + ms[j + 2], ms[j + 1], cy, cxa + j, phase);
+  unsigned px[16];
+  const bool left = X0 == 0;       // pixel 0 is image column 0: pixels 0 and 1 share the site of column 1
+  const int kr = cols - 1 - X0;    // the pixel that is the image's last column (if 1 .. 15: it repeats pixel kr - 1)
+  px[0] = v[0];
+#pragma unroll
+  for (int k = 1; k < 16; ++k) px[k] = left ? v[k - 1] : v[k];
+#pragma unroll
+  for (int k = 1; k < 16; ++k)
+    if (k == kr) px[k] = px[k - 1];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (4 * i + b < n) o |= px[4 * i + b] << (8 * b);  // (pixels beyond the ROI row were computed from zeros)
+    out[i] = o;
+  }
+}
+
+// the same 16 slot bytes from an image of format f: the segment function f names.  SENSOR false: for tables that hold no
+// YUV or Bayer entry (the kernel of such a submission is then the one it was before those existed)
+template <bool SENSOR = true, class Loads>
 __host__ __device__ inline void gather_segment_format(const Loads& mem, const uint8_t* img, const GatherFormat& f, int x, int y,
                                                       int w, int h, int r, int seg, uint32_t out[4]) {
   const size_t stride = (size_t)f.stride, img_bytes = (size_t)f.img_bytes;
+  if constexpr (SENSOR) {
+    if ((f.kind & 0xFF) == PIX_YUV) {
+      gather_segment_yuv(mem, img, img_bytes, stride, x, y, w, h, r, seg, f.big_endian, out);
+      return;
+    }
+    if ((f.kind & 0xFF) == PIX_BAYER) {
+      gather_segment_bayer(mem, img, img_bytes, stride, f.big_endian, f.rgb, x, y, w, h, r, seg, f.kind >> 8, out);
+      return;
+    }
+  }
   switch (f.bpp) {
     case 1:
       gather_segment(mem, img, img_bytes, stride, x, y, w, h, r, seg, out);

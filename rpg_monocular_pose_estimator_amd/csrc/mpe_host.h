@@ -304,14 +304,14 @@ int last_kernel_ms_of_call(mpe_handle* h, float ms[5]);  // (mpe_options.cpp)
 // it had a caller in another translation unit it was no exported name, and nothing outside the library calls it.)
 __attribute__((visibility("hidden"))) hipError_t launch_gather_rois(const GatherItem* tab, int n, uint8_t* dst, const FrameGeom& g, size_t stride, size_t img_bytes,
                               hipStream_t s);
-// the same slots from images in one of the encodings MPE_ENC_BGR8 .. MPE_ENC_MONO16 (stride and img_bytes in source
+// the same slots from images in one of the encodings MPE_ENC_BGR8 .. MPE_ENC_YUV422_YUY2 (stride and img_bytes in source
 // bytes, the ROIs of the table in pixels): the gather decodes what it reads (k_gather_rois_encoded)
 __attribute__((visibility("hidden"))) hipError_t launch_gather_rois_encoded(const GatherItem* tab, int n, uint8_t* dst, const FrameGeom& g, size_t stride,
                                       size_t img_bytes, int encoding, int big_endian, hipStream_t s);
 // the same slots from images that differ in format: item e is an image of fmts[tab[e].format] (device table, every index
-// below its length — the submission builds both; k_gather_rois_formats)
+// below its length — the submission builds both; k_gather_rois_formats).  sensor: the table holds a YUV or a Bayer entry
 __attribute__((visibility("hidden"))) hipError_t launch_gather_rois_formats(const GatherItem* tab, const GatherFormat* fmts, int n, uint8_t* dst,
-                                      const FrameGeom& g, hipStream_t s);
+                                      const FrameGeom& g, bool sensor, hipStream_t s);
 // the text of mpe_last_error, for mpe_tracker.cpp (which sees only the C ABI and declares this itself; mpe_options.cpp)
 void set_error(mpe_handle* h, const char* what);
 }  // namespace mpe_host

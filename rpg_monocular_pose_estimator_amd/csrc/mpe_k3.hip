@@ -1401,7 +1401,8 @@ __global__ __launch_bounds__(64) void k_quartic_batch(const double* __restrict__
 // =============================================================================================
 // frame decode: sensor_msgs/Image payloads -> mono8 (what cv_bridge::toCvCopy(msg, MONO8) does for the node,
 // monocular_pose_estimator.cpp:147).  HBM bound, one pass: 4 output pixels per lane and step.
-// The per-pixel rules (gray_px for bgr8 / rgb8 / bgra8 / rgba8, mono16_px for mono16) are in mpe_pixel.h.
+// The per-pixel rules (gray_px for bgr8 / rgb8 / bgra8 / rgba8, mono16_px for mono16, the Y byte of yuv422 / yuv422_yuy2,
+// bayer_px for the Bayer patterns, which k_to_mono8_bayer decodes) are in mpe_pixel.h.
 // =============================================================================================
 __global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ src, size_t src_stride, size_t src_frame_stride,
                                                   int encoding, int big_endian, int rows, int cols, long long n_rows_total,
@@ -1425,6 +1426,9 @@ __global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ sr
       }
     } else if (encoding == MPE_ENC_MONO8) {
       for (int k = 0; k < n; ++k) out[k] = s[x0 + k];
+    } else if (encoding == MPE_ENC_YUV422 || encoding == MPE_ENC_YUV422_YUY2) {
+      const uint8_t* p = s + 2 * (size_t)x0 + yuv_y_byte(encoding);
+      for (int k = 0; k < n; ++k) out[k] = p[2 * k];
     } else {
       const int bpp = (encoding == MPE_ENC_BGRA8 || encoding == MPE_ENC_RGBA8) ? 4 : 3;
       const bool rgb = encoding == MPE_ENC_RGB8 || encoding == MPE_ENC_RGBA8;
@@ -1452,6 +1456,74 @@ __global__ __launch_bounds__(256) void k_to_mono8(const uint8_t* __restrict__ sr
   }
 }
 
+// The Bayer patterns (mpe_pixel.h, bayer_px): 4 output pixels per lane from the 3 x 3 surroundings of their sites, i.e.
+// from 6 source bytes of three rows.  Rows and columns are clamped at the FRAME's own edges (bayer_site), so no lane
+// reads the neighbouring frame of the batch or a byte behind the last one; a frame below 3 x 3 is all zeros.  Each
+// source row is read by the lanes of three output rows: once from HBM, then from L2.
+__global__ __launch_bounds__(256) void k_to_mono8_bayer(const uint8_t* __restrict__ src, size_t src_stride,
+                                                        size_t src_frame_stride, int phase, int rows, int cols,
+                                                        long long n_rows_total, uint8_t* __restrict__ dst) {
+  const int quads = (cols + 3) >> 2;  // 4 output pixels per work item
+  const long long total = n_rows_total * quads;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long row = i / quads;
+    const int x0 = (int)(i - row * quads) * 4;
+    const long long f = row / rows;
+    const int y = (int)(row - f * rows);
+    uint8_t* d = dst + ((size_t)f * rows + y) * cols + x0;
+    const int n = min(4, cols - x0);
+    unsigned out[4] = {0, 0, 0, 0};
+    if (rows >= 3 && cols >= 3) {
+      const int cy = bayer_site(y, rows);
+      const uint8_t* s = src + (size_t)f * src_frame_stride + (size_t)(cy - 1) * src_stride;
+      // source columns x0 - 1 .. x0 + 4, each clamped into the row; the sums per column: up + down, and the middle row
+      // (the four middle ones as one aligned 32-bit load where the row allows it)
+      const int cl = max(x0 - 1, 0), cr = min(x0 + 4, cols - 1);
+      unsigned b[3][6];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const uint8_t* p = s + (size_t)q * src_stride;
+        b[q][0] = p[cl];
+        b[q][5] = p[cr];
+        if (n == 4 && ((reinterpret_cast<uintptr_t>(p + x0) & 3) == 0)) {
+          const unsigned w = *reinterpret_cast<const unsigned*>(p + x0);
+          b[q][1] = w & 0xFF, b[q][2] = (w >> 8) & 0xFF, b[q][3] = (w >> 16) & 0xFF, b[q][4] = w >> 24;
+        } else {
+#pragma unroll
+          for (int j = 1; j < 5; ++j) b[q][j] = p[min(x0 - 1 + j, cols - 1)];
+        }
+      }
+      unsigned vs[6], ms[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        vs[j] = b[0][j] + b[2][j];
+        ms[j] = b[1][j];
+      }
+      unsigned v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)  // the value AT column x0 + k (of use where that is an interior column)
+        v[k] = bayer_px(vs[k] + vs[k + 2], vs[k + 1], ms[k] + ms[k + 2], ms[k + 1], cy, x0 + k, phase);
+      // the first column takes the second one's value and the last column the one in front of it; the second one of
+      // a quad is in this quad (cols >= 3), the one in front of the last may be the previous quad's last
+      unsigned before = 0;
+      if (x0 > 0 && x0 == cols - 1) {  // (x0 - 1 >= 1: an interior column, whose surroundings are x0 - 2 .. x0)
+        const unsigned l2 = s[x0 - 2], l2m = s[src_stride + x0 - 2], l2d = s[2 * src_stride + x0 - 2];
+        before = bayer_px(l2 + l2d + vs[1], vs[0], l2m + ms[1], ms[0], cy, x0 - 1, phase);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int x = x0 + k;
+        out[k] = x == 0 ? v[1] : (x == cols - 1 ? (k ? v[k - 1] : before) : v[k]);
+      }
+    }
+    if (n == 4 && ((reinterpret_cast<uintptr_t>(d) & 3) == 0)) {
+      *reinterpret_cast<unsigned*>(d) = out[0] | (out[1] << 8) | (out[2] << 16) | (out[3] << 24);
+    } else {
+      for (int k = 0; k < n; ++k) d[k] = (uint8_t)out[k];
+    }
+  }
+}
+
 hipError_t launch_to_mono8(const uint8_t* src, size_t src_stride, size_t src_frame_stride, int encoding, int big_endian,
                            int n_frames, int rows, int cols, uint8_t* dst, hipStream_t s) {
   if (n_frames <= 0 || rows <= 0 || cols <= 0) return hipSuccess;
@@ -1460,6 +1532,11 @@ hipError_t launch_to_mono8(const uint8_t* src, size_t src_stride, size_t src_fra
   long long blocks = (items + 255) / 256;
   const long long most = (long long)device_cu_count() * 64;  // grid-stride beyond 64 blocks per CU
   if (blocks > most) blocks = most;
+  if (encoding_kind(encoding) == PIX_BAYER) {
+    hipLaunchKernelGGL(k_to_mono8_bayer, dim3((unsigned)blocks), dim3(256), 0, s, src, src_stride, src_frame_stride,
+                       bayer_phase(encoding), rows, cols, n_rows, dst);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_to_mono8, dim3((unsigned)blocks), dim3(256), 0, s, src, src_stride, src_frame_stride, encoding,
                      big_endian, rows, cols, n_rows, dst);
   return hipGetLastError();

@@ -5,6 +5,11 @@
 //       Y = (B * 1868 + G * 9617 + R * 4899 + 2^13) >> 14   (OpenCV 2.4, 3.0 .. 3.4.1; from 3.4.2 on: 15 bits, see mpe.h)
 //   mono16 (host byte order after cv_bridge's endianness fix): Mat::convertTo(CV_8U, 255. / 65535.) —
 //       saturate_cast<uchar>((float)v * (float)(255. / 65535.)), i.e. round-half-even of the single-precision product
+//   yuv422 (U Y V Y) / yuv422_yuy2 (Y U Y V): COLOR_YUV2GRAY_UYVY / _YUY2 — the pixel's Y byte, byte 1 / byte 0 of its
+//       two source bytes (yuv_y_byte), an exact copy
+//   bayer_rggb8 / bggr8 / gbrg8 / grbg8: COLOR_Bayer*2GRAY, OpenCV's scalar Bayer2Gray (bayer_px): the 3 x 3 surroundings
+//       of an INTERIOR pixel, every neighbour weighted by the 14-bit weight of its own colour; the border rows and
+//       columns repeat their inner neighbours (bayer_site) and an image below 3 x 3 is all zeros.  Unpinned: see mpe.h
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -33,15 +38,57 @@ __host__ __device__ inline unsigned mono16_px(unsigned v) {
   return (unsigned)r;
 }
 
-// source bytes per pixel of an MPE_ENC_* encoding, 0 for anything else (Bayer, YUV: MPE_ERR_UNSUPPORTED)
+// what decodes a pixel.  Bytes per pixel do not say it: Bayer shares 1 with mono8, YUV shares 2 with mono16
+enum PixelKind { PIX_NONE = 0, PIX_PLAIN = 1, PIX_YUV = 2, PIX_BAYER = 3 };  // PLAIN: mono8, colour, mono16
+__host__ __device__ inline int encoding_kind(int encoding) {
+  if (encoding >= MPE_ENC_MONO8 && encoding <= MPE_ENC_MONO16) return PIX_PLAIN;
+  if (encoding >= MPE_ENC_BAYER_RGGB8 && encoding <= MPE_ENC_BAYER_GRBG8) return PIX_BAYER;
+  if (encoding == MPE_ENC_YUV422 || encoding == MPE_ENC_YUV422_YUY2) return PIX_YUV;
+  return PIX_NONE;
+}
+
+// source bytes per pixel of an MPE_ENC_* encoding, 0 for anything else (MPE_ERR_UNSUPPORTED)
 __host__ __device__ inline int encoding_bytes_per_pixel(int encoding) {
   switch (encoding) {
     case MPE_ENC_MONO8: return 1;
     case MPE_ENC_MONO16: return 2;
     case MPE_ENC_BGR8: case MPE_ENC_RGB8: return 3;
     case MPE_ENC_BGRA8: case MPE_ENC_RGBA8: return 4;
+    case MPE_ENC_BAYER_RGGB8: case MPE_ENC_BAYER_BGGR8: case MPE_ENC_BAYER_GBRG8: case MPE_ENC_BAYER_GRBG8: return 1;
+    case MPE_ENC_YUV422: case MPE_ENC_YUV422_YUY2: return 2;
     default: return 0;
   }
+}
+
+// which of a YUV 4:2:2 pixel's two source bytes is its Y: 1 for yuv422 (U Y V Y), 0 for yuv422_yuy2 (Y U Y V)
+__host__ __device__ inline int yuv_y_byte(int encoding) { return encoding == MPE_ENC_YUV422 ? 1 : 0; }
+
+// Bayer phase: the parities of the rows (bit 1) and columns (bit 0) that hold the RED sites; blue sits on the other
+// parity of both, green on the rest.  rggb 0, grbg 1, gbrg 2, bggr 3
+__host__ __device__ inline int bayer_phase(int encoding) {
+  switch (encoding) {
+    case MPE_ENC_BAYER_GRBG8: return 1;
+    case MPE_ENC_BAYER_GBRG8: return 2;
+    case MPE_ENC_BAYER_BGGR8: return 3;
+    default: return 0;
+  }
+}
+
+// the interior site whose value output pixel v (a row or a column index) of n takes; n >= 3
+__host__ __device__ inline int bayer_site(int v, int n) { return v < 1 ? 1 : (v > n - 2 ? n - 2 : v); }
+
+// One interior site (y, x) — IMAGE coordinates, they give the colour — from the sums over its 3 x 3 surroundings:
+// diag = the four diagonal neighbours, vert = up + down, horiz = left + right, c = the centre.
+__host__ __device__ inline unsigned bayer_px(unsigned diag, unsigned vert, unsigned horiz, unsigned c, int y, int x,
+                                             int phase) {
+  const bool red_row = (y & 1) == (phase >> 1), red_col = (x & 1) == (phase & 1);
+  if (red_row == red_col) {  // a red or a blue site: the diagonals have the other colour, the edges are green
+    const unsigned wx = red_row ? 4899u : 1868u, wz = red_row ? 1868u : 4899u;
+    return (wz * diag + 9617u * (vert + horiz) + 4u * wx * c + (1u << 15)) >> 16;
+  }
+  // a green site: red left and right in a red row (blue above and below), the other way round in a blue row
+  const unsigned wh = red_row ? 4899u : 1868u, wv = red_row ? 1868u : 4899u;
+  return (wv * vert + wh * horiz + 2u * 9617u * c + (1u << 14)) >> 15;
 }
 
 }  // namespace mpe

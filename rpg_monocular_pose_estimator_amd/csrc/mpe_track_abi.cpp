@@ -274,15 +274,24 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     else
       pack_roi(mb + head_bytes + (size_t)k * slot, g, it, fm ? fm->formats[fm->item_format[i]].stride_bytes : stride_bytes);
   }
+  bool sensor_formats = false;  // the table holds a YUV or a Bayer entry
   if (source == kFormatDeviceFrames) {
     GatherFormat* tab = reinterpret_cast<GatherFormat*>(mb + fmt_off);
     for (int f = 0; f < fm->n_formats; ++f) {
       const mpe_image_format& mf = fm->formats[f];
       const int bpp = encoding_bytes_per_pixel(mf.encoding);
+      const int kind = encoding_kind(mf.encoding);
+      sensor_formats |= kind != PIX_PLAIN;
       tab[f] = GatherFormat{(uint64_t)mf.stride_bytes,
                             (uint64_t)((size_t)(mf.rows - 1) * mf.stride_bytes + (size_t)mf.cols * (size_t)bpp), bpp,
                             mf.encoding == MPE_ENC_RGB8 || mf.encoding == MPE_ENC_RGBA8,
-                            mf.encoding == MPE_ENC_MONO16 && mf.src_big_endian, 0};
+                            mf.encoding == MPE_ENC_MONO16 && mf.src_big_endian, kind};
+      if (kind == PIX_YUV) tab[f].big_endian = yuv_y_byte(mf.encoding);
+      if (kind == PIX_BAYER) {  // (the neighbourhood decode clamps at the image's edges: its size, and the pattern)
+        tab[f].rgb = mf.cols;
+        tab[f].big_endian = mf.rows;
+        tab[f].kind = PIX_BAYER | (bayer_phase(mf.encoding) << 8);
+      }
     }
   }
   uint8_t* host_rec = mb + ((staged_bytes + 255) & ~(size_t)255);
@@ -315,7 +324,7 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   else if (source == kFormatDeviceFrames)
     HIP_TRY(h, launch_gather_rois_formats(reinterpret_cast<const GatherItem*>(d_in + gat_off),
                                           reinterpret_cast<const GatherFormat*>(d_in + fmt_off), n, d_in + head_bytes, g,
-                                          h->stream));
+                                          sensor_formats, h->stream));
   if (wide) {
     h->pending_track_rec = host_rec;  // (for run_wide_slots, which follows at once: nothing stays pending)
     return MPE_OK;
@@ -462,7 +471,7 @@ int mpe_track_step_batch_setups_device_encoded_submit(mpe_handle* h, const mpe_t
   if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || rows < 1 || cols < 1)
     return fail(h, MPE_ERR_ARG, "bad argument");
   const size_t bpp = (size_t)encoding_bytes_per_pixel(encoding);
-  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)");
   if (stride_bytes < (size_t)cols * bpp) return fail(h, MPE_ERR_ARG, "bad argument");
   if (encoding == MPE_ENC_MONO8)  // nothing to decode: the mono8 submission and k_gather_rois
     return mpe_track_step_batch_setups_device_submit(h, items, item_setup, n, rows, cols, stride_bytes, setups, n_setups);
@@ -506,7 +515,9 @@ int mpe_track_step_batch_formats_submit(mpe_handle* h, const mpe_track_item* ite
     return fail(h, MPE_ERR_ARG, "bad argument");
   for (int f = 0; f < n_formats; ++f) {
     const size_t bpp = (size_t)encoding_bytes_per_pixel(formats[f].encoding);
-    if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+    if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)");
+    if (!frames_on_device && encoding_kind(formats[f].encoding) != PIX_PLAIN)  // (what these codes answered before)
+      return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported for host frames (Bayer and YUV: device frames)");
     if (formats[f].rows < 1 || formats[f].cols < 1 || formats[f].stride_bytes < (size_t)formats[f].cols * bpp)
       return fail(h, MPE_ERR_ARG, "bad argument");
   }
@@ -634,7 +645,9 @@ int mpe_track_step_batch_wide(mpe_handle* h, const mpe_track_item* items, const 
       !dets_out || !corr_out || !out)
     return fail(h, MPE_ERR_ARG, "bad argument");
   const size_t bpp = (size_t)encoding_bytes_per_pixel(encoding);
-  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)");
+  if (!frames_on_device && encoding_kind(encoding) != PIX_PLAIN)  // (what these codes answered before they existed)
+    return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported for host frames (Bayer and YUV: device frames)");
   if (!frames_on_device && encoding != MPE_ENC_MONO8)
     return fail(h, MPE_ERR_ARG, "host frames are mono8 (the encodings are decoded from device frames)");
   if (stride_bytes < (size_t)cols * bpp) return fail(h, MPE_ERR_ARG, "bad argument");

@@ -983,7 +983,7 @@ extern "C" {
 static int check_encoding(mpe_handle* h, int encoding, int cols, size_t stride_bytes) {
   const int bpp = mpe::encoding_bytes_per_pixel(encoding);
   if (!bpp) {
-    mpe_host::set_error(h, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+    mpe_host::set_error(h, "encoding not supported (one of MPE_ENC_*)");
     return MPE_ERR_UNSUPPORTED;
   }
   if (encoding != MPE_ENC_MONO8 && (cols < 1 || stride_bytes < (size_t)cols * (size_t)bpp)) {
@@ -1066,7 +1066,11 @@ static int check_formats(mpe_handle* h, const mpe_image_format* formats, int n, 
     const mpe_image_format& f = formats[i];
     const int bpp = mpe::encoding_bytes_per_pixel(f.encoding);
     if (!bpp) {
-      mpe_host::set_error(h, "encoding not supported (mono8, bgr8, rgb8, bgra8, rgba8, mono16)");
+      mpe_host::set_error(h, "encoding not supported (one of MPE_ENC_*)");
+      return MPE_ERR_UNSUPPORTED;
+    }
+    if (!on_device && mpe::encoding_kind(f.encoding) != mpe::PIX_PLAIN) {  // (what these codes answered before)
+      mpe_host::set_error(h, "encoding not supported for host frames (Bayer and YUV: device frames)");
       return MPE_ERR_UNSUPPORTED;
     }
     if (f.rows < 1 || f.cols < 1 || f.stride_bytes < (size_t)f.cols * (size_t)bpp) {
