@@ -746,6 +746,54 @@ int mpe_tracker_get_image_points(mpe_tracker* t, double* xy, int cap_points);
 /* distorted_detection_centers_ of the last detection (what the overlay circles, pose_estimator.cpp:44-48) */
 int mpe_tracker_get_distorted_centers(mpe_tracker* t, float* xy, int cap_points);
 
+/* ---- several cameras, one body: the cameras of a calibrated rig fused into ONE pose (joint Gauss-Newton) ----
+ * A rig has 1 .. MPE_RIG_MAX_CAMERAS cameras; camera c has K_c and a rigid extrinsic T_cam_rig = E_c = [R_c | t_c],
+ * camera <- rig, row-major 4x4 (trusted: the upper 3x4 is used as it is, orthonormality is not checked).  The unknown
+ * is T, rig <- marker frame.  The refinement is PoseEstimator::optimisePose (pose_estimator.cpp:733-792) over rows
+ * (camera, marker xyz, undistorted pixel uv) that bring their own camera: per row q = E_c T p, the residual and the
+ * closed-form Jacobian of computeJacobian (:945-957) at q with K_c, times the 6x6 adjoint of E_c (twist order
+ * (upsilon, omega)); A = sum J^T J and b = sum J^T e in row order, unpivoted LDL^T, T <- exp(dT) T, stop at
+ * max|dT| <= 1e-13 or after 500 iterations, cov = A^-1 of the last iteration: the covariance of a left twist in the RIG
+ * frame.  One camera with the identity extrinsic gives mpe_optimise_pose's pose, covariance and count, bit for bit. */
+#define MPE_RIG_MAX_CAMERAS 16
+typedef struct mpe_rig_camera {
+  double K[9];
+  double T_cam_rig[16];
+} mpe_rig_camera;
+
+/* Stage entry: n_problems problems over ONE rig; the rows of problem i are [row_begin[i], row_begin[i+1]) of
+ * row_camera / row_marker_xyz (x 3) / row_uv (x 2), at most MPE_RIG_MAX_CAMERAS * MPE_MAX_MARKERS = 256 of them, in
+ * summation order (camera after camera, each in its correspondence order).  T_init: n x 16; out: n HOST records —
+ * T (rig <- marker), cov, gn_iterations, n_corr = rows used, n_det = cameras that contributed a row, status
+ * MPE_FRAME_POSE, or MPE_FRAME_NO_POSE with fewer than 3 rows (T = T_init, cov = 0) or a non-finite final pose.  Rank
+ * deficiency beyond that is the caller's concern, as in the reference.  One input copy, one launch (a wave per
+ * problem; a problem's record does not depend on the rest of the batch) and one copy back on the handle's stream.
+ * MPE_ERR_ARG: a null pointer, n_cameras outside 1 .. 16, a camera index outside the rig, a decreasing row_begin, a
+ * submission of the handle that is not collected yet; MPE_ERR_UNSUPPORTED: more than 256 rows in a problem; no record
+ * is written then.  n_problems == 0: MPE_OK, nothing submitted. */
+int mpe_rig_optimise_pose_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const int* row_begin,
+                                const int* row_camera, const double* row_marker_xyz, const double* row_uv,
+                                int n_problems, const double* T_init, mpe_result* out);
+
+/* After a lock-step call over the n trackers of a rig (one per camera, all on one handle, one marker set = one body):
+ * fuse those whose frame updated (updated[i] != 0; NULL = all).  Tracker i brings its K, its markers and the rows of
+ * its last correspondences over its image points (mpe_tracker_get_correspondences / _get_image_points), T_cam_rig
+ * (n x 16) its extrinsic; the start is E_c^-1 * pose_c of the first contributing tracker.  One problem through
+ * mpe_rig_optimise_pose_batch.  rows_per_camera (optional, n ints).  Returns 1 fused (rig_out->status MPE_FRAME_POSE),
+ * 0 no pose (no tracker contributed, or the status above), MPE_ERR_ARG before any device work for trackers on
+ * different handles, repeated trackers, differing marker sets, or n outside 1 .. 16. */
+int mpe_rig_fuse_trackers(mpe_tracker* const* trackers, int n, const double* T_cam_rig, const int* updated,
+                          mpe_result* rig_out, int* rows_per_camera);
+
+/* Give trackers a pose from the rig — host state only (what mpe_tracker_get_state / _set_state move).  For every i with
+ * seed[i] != 0: current_pose = predicted_pose = E_i * rig_pose, current_time = time; with rig_prev_pose also
+ * previous_pose = E_i * rig_prev_pose, previous_time = prev_time and it_since_initialized = 2 (the next frame predicts
+ * with the constant-velocity model), without it it_since_initialized = 1.  Covariance and ROI are left alone.  The next
+ * frame of such a tracker takes the reference's tracking branch (predictWithROI, nearest neighbour, validation, fallback
+ * to initialise() as ever) instead of the brute force. */
+int mpe_rig_seed_trackers(mpe_tracker* const* trackers, int n, const double* T_cam_rig, const int* seed,
+                          const double rig_pose[16], double time, const double* rig_prev_pose, double prev_time);
+
 /* Stage-level batch entry points (used by the parity tests at every stage boundary). */
 /* detection only (a1): dets is a HOST array of n_frames records */
 int mpe_detect_batch(mpe_handle* h, const uint8_t* frames, int n_frames, int rows, int cols,

@@ -52,6 +52,13 @@ class MpeDetectionsWide(C.Structure):  # mpe_detections_wide
                 ("dist_xy", C.c_float * (2 * WIDE_DETECTIONS))]
 
 
+RIG_MAX_CAMERAS = 16  # MPE_RIG_MAX_CAMERAS
+
+
+class MpeRigCamera(C.Structure):  # mpe_rig_camera
+    _fields_ = [("K", C.c_double * 9), ("T_cam_rig", C.c_double * 16)]
+
+
 RESULT_DTYPE = np.dtype([("T", "f8", (16,)), ("cov", "f8", (36,)), ("status", "i4"), ("n_det", "i4"),
                          ("n_corr", "i4"), ("gn_iterations", "i4")])
 DETECTIONS_DTYPE = np.dtype([("n", "i4"), ("status", "i4"), ("undist_xy", "f8", (2 * MAX_DETECTIONS,)),
@@ -108,7 +115,7 @@ def source_fingerprint():
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
                                   "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
-                                  "mpe_wide_nn.h"):
+                                  "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig.cpp"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -250,6 +257,12 @@ def load_library():
                                              dp, C.c_int, dp, dp, C.c_int, C.POINTER(MpeParams), C.c_void_p]
     lib.mpe_estimate_batch_multi_device.argtypes = [hp, C.c_int, hp, C.POINTER(C.c_int), C.c_int, C.c_int, dp, C.c_int,
                                                     dp, dp, C.c_int, C.POINTER(MpeParams), C.c_void_p]
+    # the cameras of a rig fused into one body pose
+    lib.mpe_rig_optimise_pose_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, dp, dp, C.c_int, dp, C.c_void_p]
+    lib.mpe_rig_fuse_trackers.argtypes = [hp, C.c_int, dp, ip, C.c_void_p, ip]
+    lib.mpe_rig_seed_trackers.argtypes = [hp, C.c_int, dp, ip, dp, C.c_double, dp, C.c_double]
+    lib.mpe_tracker_get_correspondences.argtypes = [C.c_void_p, up, C.c_int]
+    lib.mpe_tracker_get_image_points.argtypes = [C.c_void_p, dp, C.c_int]
     _lib = lib
     return lib
 
@@ -955,6 +968,32 @@ class Handle:
         return dict(status=res.status, T=np.array(res.T).reshape(4, 4), cov=np.array(res.cov).reshape(6, 6),
                     gn_iterations=res.gn_iterations)
 
+    def rig_optimise_pose_batch(self, cameras, problems, T_init):
+        """mpe_rig_optimise_pose_batch: the joint Gauss-Newton of a rig's cameras, a batch of problems over ONE rig in
+        one launch.  cameras: a list of (K 3x3, T_cam_rig 4x4, camera <- rig); problems: a list of row lists, a row =
+        (camera index, marker xyz, undistorted pixel uv), in summation order; T_init: (n, 4, 4), rig <- marker frame.
+        -> records [RESULT_DTYPE] (n): T, cov (left twist in the rig frame), status, gn_iterations, n_corr = rows,
+        n_det = cameras with a row."""
+        cams = (MpeRigCamera * max(1, len(cameras)))()
+        for c, (K, E) in zip(cams, cameras):
+            c.K[:] = _f64(K).reshape(9)
+            c.T_cam_rig[:] = _f64(E).reshape(16)
+        n = len(problems)
+        begin = np.zeros(n + 1, np.int32)
+        begin[1:] = np.cumsum([len(rows) for rows in problems])
+        flat = [r for rows in problems for r in rows]
+        cam = np.ascontiguousarray([r[0] for r in flat], np.int32).reshape(-1)
+        xyz = _f64([r[1] for r in flat]).reshape(-1, 3)
+        uv = _f64([r[2] for r in flat]).reshape(-1, 2)
+        T0 = _f64(T_init).reshape(-1, 16)
+        assert len(T0) == n
+        rec = np.zeros(n, RESULT_DTYPE)
+        ip = C.POINTER(C.c_int)
+        rc = self._lib.mpe_rig_optimise_pose_batch(self._h, cams, len(cameras), begin.ctypes.data_as(ip),
+                                                   cam.ctypes.data_as(ip), _dp(xyz), _dp(uv), n, _dp(T0), rec.ctypes.data)
+        self._check(rc, "mpe_rig_optimise_pose_batch")
+        return rec
+
     # ---- one tracked frame: findLeds(ROI) + findCorrespondences + checkCorrespondences + optimisePose ----
     def track_step(self, img, roi, params, K, D, markers, predicted_px):
         img = np.ascontiguousarray(img, np.uint8)
@@ -1284,6 +1323,20 @@ class Tracker:
                     roi=tuple(info[0:4]), it_since_initialized=info[4], n_det=info[5], n_corr=info[6],
                     used_bruteforce=bool(info[7]))
 
+    def correspondences(self):
+        """getCorrespondences(): the rows (marker, detection), 1-based, of the last frame that made any -> (n, 2) uint32."""
+        n = self._lib.mpe_tracker_get_correspondences(self._t, None, 0)
+        corr = np.zeros((max(n, 0), 2), np.uint32)
+        self._lib.mpe_tracker_get_correspondences(self._t, corr.ctypes.data_as(C.POINTER(C.c_uint32)), len(corr))
+        return corr
+
+    def image_points(self):
+        """getImagePoints(): the undistorted detections of the last frame -> (n, 2) float64."""
+        n = self._lib.mpe_tracker_get_image_points(self._t, None, 0)
+        xy = np.zeros((max(n, 0), 2))
+        self._lib.mpe_tracker_get_image_points(self._t, _dp(xy), len(xy))
+        return xy
+
     def run_sequence(self, frames, times):
         """The image-callback loop in C over a recorded sequence (frames (n,rows,cols) uint8, C-contiguous).
         -> (records [RESULT_DTYPE], info (n,8) int32).  ctypes drops the GIL for the duration."""
@@ -1310,3 +1363,59 @@ class Tracker:
             self.close()
         except Exception:
             pass
+
+
+class Rig:
+    """The cameras of a calibrated rig that see ONE body: a lock-step group of trackers (one per camera, one handle, one
+    marker set) plus the extrinsics T_cam_rig (n, 4, 4), camera <- rig, trusted as given.  step() drives the group's
+    lock-step entry, then fuses the cameras that updated into one pose, rig <- marker frame, with one covariance
+    (mpe_rig_fuse_trackers: the joint Gauss-Newton on the device)."""
+
+    def __init__(self, handle, trackers, T_cam_rig):
+        self.handle = handle
+        self.trackers = list(trackers)
+        self.T_cam_rig = _f64(T_cam_rig).reshape(len(self.trackers), 16)
+        self._ts = (C.c_void_p * len(self.trackers))(*[t._t for t in self.trackers])
+        self._prev = None  # (rig pose, time) of the previous step when it fused
+
+    def fuse(self, updated=None):
+        """mpe_rig_fuse_trackers over the trackers' last frames -> (fused, record [RESULT_DTYPE] (1), rows per camera)."""
+        lib, n = self.handle._lib, len(self.trackers)
+        rec = np.zeros(1, RESULT_DTYPE)
+        rows = np.zeros(n, np.int32)
+        upd = None if updated is None else np.ascontiguousarray(updated, np.int32)
+        ip = C.POINTER(C.c_int)
+        rc = lib.mpe_rig_fuse_trackers(self._ts, n, _dp(self.T_cam_rig), None if upd is None else upd.ctypes.data_as(ip),
+                                       rec.ctypes.data, rows.ctypes.data_as(ip))
+        if rc < 0:
+            raise MpeError("mpe_rig_fuse_trackers failed (%d): %s" % (rc, lib.mpe_last_error(self.handle._h).decode()))
+        return bool(rc), rec, rows
+
+    def seed(self, seed, rig_pose, time, rig_prev_pose=None, prev_time=0.0):
+        """mpe_rig_seed_trackers: the trackers with seed[i] != 0 get their pose from the rig's (host state only)."""
+        lib, n = self.handle._lib, len(self.trackers)
+        sd = np.ascontiguousarray(seed, np.int32)
+        prev = None if rig_prev_pose is None else _dp(_f64(rig_prev_pose).reshape(16))
+        rc = lib.mpe_rig_seed_trackers(self._ts, n, _dp(self.T_cam_rig), sd.ctypes.data_as(C.POINTER(C.c_int)),
+                                       _dp(_f64(rig_pose).reshape(16)), float(time), prev, float(prev_time))
+        if rc < 0:
+            raise MpeError("mpe_rig_seed_trackers failed (%d)" % rc)
+
+    def step(self, imgs, times, formats=None, reseed=False):
+        """One time step: imgs[i] / times[i] camera i's frame and stamp.  Cameras of one image shape go through
+        tracker_estimate_batch_mixed, others (or formats given: as tracker_estimate_batch_formats takes them) through
+        tracker_estimate_batch_formats; then the fusion.  reseed: the trackers that did NOT update get the rig's pose
+        (and the previous step's, when that step fused), so that their next frame tracks instead of running the brute
+        force.  -> (records (N), info (N, 8), updated (N) — the lock-step entry's, unchanged —, rig record (1), fused)."""
+        same = formats is None and not _is_torch(imgs[0]) and len({(np.shape(im), np.asarray(im).strides[0]) for im in imgs}) == 1
+        if same:
+            rec, info, upd = tracker_estimate_batch_mixed(self.trackers, imgs, times)
+        else:
+            rec, info, upd = tracker_estimate_batch_formats(self.trackers, imgs, times, formats)
+        fused, rig, _ = self.fuse(upd)
+        t = float(np.max(_f64(times)))
+        if reseed and fused and not upd.all():
+            prev = self._prev
+            self.seed(~upd, rig["T"][0], t, None if prev is None else prev[0], 0.0 if prev is None else prev[1])
+        self._prev = (rig["T"][0].copy(), t) if fused else None
+        return rec, info, upd, rig, fused

@@ -201,6 +201,12 @@ hipError_t launch_k1b_general_wide(const uint8_t* frames, const unsigned long lo
 // over a wide record, then k3_peel_wide's hand-over (compact / corr_compact / slot_wide as below)
 hipError_t launch_k_nn_wide(const mpe_detections_wide* dets, const double* pred, int n_items, int n_markers, double nn_tol,
                             mpe_detections* compact, uint32_t* corr_compact, uint32_t* slot_wide, hipStream_t s);
+// k_rig_refine, one wave per problem: the joint Gauss-Newton of a rig's cameras (mpe_rig_gn.h).  Problem i owns the rows
+// [row_begin[i], row_begin[i + 1]) (at most 256, camera indices below n_cam: the caller checks), starts from T_init +
+// 16 i and fills out[i]; everything in device memory.
+hipError_t launch_k_rig_refine(const mpe_rig_camera* cams, int n_cam, const int* row_begin, const int* row_cam,
+                               const double* row_xyz, const double* row_uv, const double* T_init, int n_problems,
+                               mpe_result* out, hipStream_t s);
 hipError_t launch_k2_vote_wide(const mpe_detections_wide* dets, const SolveParams& sp, const BruteBlock* blocks,
                                int n_blocks, uint32_t* hist, hipStream_t s);
 hipError_t launch_k3_peel_wide(const mpe_detections_wide* dets, const uint32_t* hist, int n_items, int n_markers,

@@ -271,6 +271,7 @@ __device__ __forceinline__ int k3_gauss_newton(int n_c, Row row, double fx, doub
 #define K3_GROUP 16                 // lanes cooperating on one frame in the validation kernel
 #define K3_FRAMES_PER_BLOCK 4       // one wave = 4 frames
 #define K3B_THREADS 64              // refinement kernel: one lane per frame
+#include "mpe_rig_gn.h"            // (k_rig_refine's logic, shared with the CPU tier: behind the tail helpers it builds on)
 
 // What the validation kernel hands to the refinement kernel, one record per frame (global memory).
 struct TailMid {
@@ -1311,6 +1312,37 @@ hipError_t launch_k_nn_wide(const mpe_detections_wide* dets, const double* pred,
   if (n_items <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_nn_wide, dim3((unsigned)n_items), dim3(64), 0, s, dets, pred, n_items, n_markers, nn_tol, compact,
                      corr_compact, slot_wide);
+  return hipGetLastError();
+}
+
+// The cameras of a rig fused into one body pose (mpe_rig_optimise_pose_batch): optimisePose over rows that bring their
+// own camera (mpe_rig_gn.h), ONE WAVE PER PROBLEM and one block per problem — lanes take rows l, l + 64, ... of up to
+// MPE_RIG_MAX_ROWS and write their Jacobian and residual rows to LDS, 27 lanes sum the 21 + 6 entries of the normal
+// equations over the rows in row order, LDL^T / solve / exponential map / covariance as k3b_group_body runs them.  A
+// block reads only its own problem's rows and start pose and the rig's cameras, and keeps everything else in its own
+// LDS: the record does not depend on the block's place in the launch or on the other problems.  The host has checked
+// the row counts and camera indices; the row count is clamped all the same.
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_refine(const mpe_rig_camera* __restrict__ cams, int n_cam,
+                                                              const int* __restrict__ row_begin,
+                                                              const int* __restrict__ row_cam,
+                                                              const double* __restrict__ row_xyz,
+                                                              const double* __restrict__ row_uv,
+                                                              const double* __restrict__ T_init, int n_problems,
+                                                              mpe_result* __restrict__ out) {
+  __shared__ RigGnLds s_rig;
+  const int i = blockIdx.x;
+  if (i >= n_problems) return;  // (block-uniform)
+  const int b = row_begin[i];
+  const int n = min(max(row_begin[i + 1] - b, 0), MPE_RIG_MAX_ROWS);
+  rig_gn_refine(s_rig, cams, n_cam, row_cam + b, row_xyz + 3 * (size_t)b, row_uv + 2 * (size_t)b, n,
+                T_init + 16 * (size_t)i, out + i);
+}
+hipError_t launch_k_rig_refine(const mpe_rig_camera* cams, int n_cam, const int* row_begin, const int* row_cam,
+                               const double* row_xyz, const double* row_uv, const double* T_init, int n_problems,
+                               mpe_result* out, hipStream_t s) {
+  if (n_problems <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rig_refine, dim3((unsigned)n_problems), dim3(MPE_RIG_LANES), 0, s, cams, n_cam, row_begin, row_cam,
+                     row_xyz, row_uv, T_init, n_problems, out);
   return hipGetLastError();
 }
 

@@ -462,6 +462,105 @@ int mpe_tracker_get_distorted_centers(mpe_tracker* t, float* xy, int cap_points)
   return (int)t->det_dist.size() / 2;
 }
 
+// ---- the trackers of a rig: one body seen by several cameras -----------------------------------------
+// (the joint refinement itself is mpe_rig_optimise_pose_batch, mpe_rig.cpp; here only what reads or sets tracker state)
+static Mat4 mat4_from(const double* m) {
+  Mat4 r;
+  std::memcpy(r.a, m, sizeof(r.a));
+  return r;
+}
+
+int mpe_rig_fuse_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const int* updated, mpe_result* rig_out,
+                          int* rows_per_camera) {
+  if (!ts || n < 1 || !ts[0]) return MPE_ERR_ARG;
+  mpe_handle* h = ts[0]->h;
+  if (n > MPE_RIG_MAX_CAMERAS) {
+    mpe_host::set_error(h, "n outside 1 .. MPE_RIG_MAX_CAMERAS");
+    return MPE_ERR_ARG;
+  }
+  if (!T_cam_rig || !rig_out) {
+    mpe_host::set_error(h, "bad argument");
+    return MPE_ERR_ARG;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!ts[i]) {
+      mpe_host::set_error(h, "bad argument");
+      return MPE_ERR_ARG;
+    }
+    if (ts[i]->h != h) {
+      mpe_host::set_error(h, "the trackers of a rig must be on one handle");
+      return MPE_ERR_ARG;
+    }
+    for (int j = 0; j < i; ++j)
+      if (ts[j] == ts[i]) {
+        mpe_host::set_error(h, "a tracker is given twice");
+        return MPE_ERR_ARG;
+      }
+    if (ts[i]->markers != ts[0]->markers) {
+      mpe_host::set_error(h, "the trackers of a rig must share one marker set (one body)");
+      return MPE_ERR_ARG;
+    }
+  }
+  std::vector<mpe_rig_camera> cams((size_t)n);
+  std::vector<int> row_cam;
+  std::vector<double> xyz, uv;
+  int first = -1;
+  for (int i = 0; i < n; ++i) {
+    const mpe_tracker* t = ts[i];
+    std::memcpy(cams[(size_t)i].K, t->K, sizeof(t->K));
+    std::memcpy(cams[(size_t)i].T_cam_rig, T_cam_rig + 16 * (size_t)i, 16 * sizeof(double));
+    int rows = 0;
+    if (!updated || updated[i]) {
+      const int n_m = n_markers(t), n_d = (int)t->det.size() / 2;
+      for (size_t r = 0; r + 1 < t->corr.size() && rows < MPE_MAX_MARKERS; r += 2) {
+        const int m = (int)t->corr[r], d = (int)t->corr[r + 1];
+        if (m < 1 || m > n_m || d < 1 || d > n_d) continue;
+        row_cam.push_back(i);
+        xyz.insert(xyz.end(), &t->markers[3 * (size_t)(m - 1)], &t->markers[3 * (size_t)(m - 1)] + 3);
+        uv.push_back(t->det[2 * (size_t)(d - 1)]);
+        uv.push_back(t->det[2 * (size_t)(d - 1) + 1]);
+        ++rows;
+      }
+      if (rows > 0 && first < 0) first = i;
+    }
+    if (rows_per_camera) rows_per_camera[i] = rows;
+  }
+  if (first < 0) {
+    std::memset(rig_out, 0, sizeof(*rig_out));
+    for (int i = 0; i < 16; i += 5) rig_out->T[i] = 1.0;
+    rig_out->status = MPE_FRAME_NO_POSE;
+    return 0;
+  }
+  const Mat4 T0 = matmul(inverse(mat4_from(cams[(size_t)first].T_cam_rig)), ts[first]->predicted);
+  const int row_begin[2] = {0, (int)row_cam.size()};
+  const int rc = mpe_rig_optimise_pose_batch(h, cams.data(), n, row_begin, row_cam.data(), xyz.data(), uv.data(), 1,
+                                             &T0.a[0][0], rig_out);
+  if (rc != MPE_OK) return rc;
+  return rig_out->status == MPE_FRAME_POSE ? 1 : 0;
+}
+
+int mpe_rig_seed_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const int* seed, const double rig_pose[16],
+                          double time, const double* rig_prev_pose, double prev_time) {
+  if (!ts || n < 1 || n > MPE_RIG_MAX_CAMERAS || !T_cam_rig || !seed || !rig_pose) return MPE_ERR_ARG;
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]) return MPE_ERR_ARG;
+  for (int i = 0; i < n; ++i) {
+    if (!seed[i]) continue;
+    mpe_tracker* t = ts[i];
+    const Mat4 E = mat4_from(T_cam_rig + 16 * (size_t)i);
+    t->current = t->predicted = matmul(E, mat4_from(rig_pose));
+    t->t_current = time;
+    if (rig_prev_pose) {
+      t->previous = matmul(E, mat4_from(rig_prev_pose));
+      t->t_previous = prev_time;
+      t->it_since_initialized = 2;
+    } else {
+      t->it_since_initialized = 1;
+    }
+  }
+  return MPE_OK;
+}
+
 // ---- N trackers in lock step -----------------------------------------------------------------------
 // The state machine of estimateBodyPose per stream, with the device steps of all streams that are at the same
 // point batched into one submission: DETECT = findLeds in the stream's ROI (+ nearest-neighbour correspondences,

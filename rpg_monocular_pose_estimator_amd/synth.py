@@ -240,6 +240,76 @@ def make_sequence(config, n, seed, dt=0.02, lin_speed=0.15, ang_speed=0.6, dropo
     return dict(frames=frames, T_true=np.array(Ts), times=np.arange(n) * dt, K=K, D=D, markers=M, rows=rows, cols=cols)
 
 
+def make_rig_sequence(config, n, seed, cameras, T_cam_rig, dropout=None, dt=0.02, lin_speed=0.15, ang_speed=0.6,
+                      max_tries=20000):
+    """One body seen by the cameras of a calibrated rig: ONE smooth trajectory in the rig frame (make_sequence's model:
+    constant twist + small jitter, frame k at time k*dt), accepted only when EVERY camera keeps all LEDs in view under
+    make_sequence's margins (80 px on the first frame, 20 px / 12 px apart / 0.5 m deep afterwards), and one rendered
+    sequence per camera.  cameras: a list of (K, D) (5 plumb-bob coefficients) or (K, D, rows, cols) — a camera without
+    a size has the config's; T_cam_rig: (N, 4, 4), camera <- rig; dropout: {camera index: frames rendered with only 2
+    LEDs}.  -> dict(frames [N arrays (n, rows_c, cols_c)], T_true (n, 4, 4) rig <- marker frame, T_true_cam (N, n, 4, 4),
+    times, cameras [(K, D, rows, cols)], T_cam_rig, markers)."""
+    cfg = CONFIGS[config] if isinstance(config, str) else config
+    M = np.asarray(cfg["markers"])
+    E = np.asarray(T_cam_rig, np.float64).reshape(-1, 4, 4)
+    cams = []
+    for c in cameras:
+        K, D = np.array(c[0], np.float64).reshape(3, 3), np.array(c[1], np.float64).reshape(-1)
+        rows, cols = (int(c[2]), int(c[3])) if len(c) > 2 else (cfg["rows"], cfg["cols"])
+        cams.append((K, D, rows, cols))
+    assert len(cams) == len(E) >= 1
+    dropout = {} if dropout is None else {int(c): set(int(k) for k in fr) for c, fr in dropout.items()}
+
+    def in_view(T_rig, margin):
+        for (K, D, rows, cols), Ec in zip(cams, E):
+            Tc = Ec @ T_rig
+            if Tc[2, 3] < 0.5 or ((Tc[:3, :3] @ M.T).T + Tc[:3, 3])[:, 2].min() <= 0.1:
+                return False
+            px = distort_px(project(Tc, M, K), K, D)
+            d = np.linalg.norm(px[:, None, :] - px[None, :, :], axis=-1) + np.eye(len(M)) * 1e9
+            if (px[:, 0].min() < margin or px[:, 0].max() > cols - 1 - margin or px[:, 1].min() < margin
+                    or px[:, 1].max() > rows - 1 - margin or d.min() < 12.0):
+                return False
+        return True
+
+    rng = np.random.default_rng([seed, 17])
+    E0_inv = np.linalg.inv(E[0])
+    for _ in range(max_tries):
+        T0c, _ = sample_scene(rng, M, cams[0][0], cams[0][1], cams[0][2], cams[0][3], 0, margin=80.0)
+        T0 = E0_inv @ T0c
+        if not in_view(T0, 80.0):
+            continue
+        v = rng.normal(size=3)
+        v *= lin_speed / np.linalg.norm(v)
+        w = rng.normal(size=3)
+        w *= ang_speed / np.linalg.norm(w)
+        Ts = []
+        for k in range(n):
+            t = k * dt
+            Tk = np.eye(4)
+            Tk[:3, :3] = rodrigues(w, np.linalg.norm(w) * t) @ T0[:3, :3]
+            Tk[:3, 3] = T0[:3, 3] + v * t + 0.0005 * rng.normal(size=3)
+            if not in_view(Tk, 20.0):
+                break
+            Ts.append(Tk)
+        if len(Ts) == n:
+            break
+    else:
+        raise ValueError("make_rig_sequence: no trajectory keeps every camera's LEDs in view (extrinsics too far apart?)")
+    frames, T_cam = [], []
+    for c, ((K, D, rows, cols), Ec) in enumerate(zip(cams, E)):
+        fr = np.empty((n, rows, cols), np.uint8)
+        for k in range(n):
+            px = distort_px(project(Ec @ Ts[k], M, K), K, D)
+            if k in dropout.get(c, ()):
+                px = px[:2]
+            fr[k] = render_frame(np.random.default_rng([seed, k, 3, c]), px, rows, cols, cfg["spot_sigma"])
+        frames.append(fr)
+        T_cam.append(np.array([Ec @ T for T in Ts]))
+    return dict(frames=frames, T_true=np.array(Ts), T_true_cam=np.array(T_cam), times=np.arange(n) * dt, cameras=cams,
+                T_cam_rig=E, markers=M)
+
+
 CLUTTER_KINDS = ("salt", "salt_dense", "patch", "ring", "grid", "d4", "d16")
 
 

@@ -31,4 +31,16 @@ WN=$(mktemp -d)/wide_nn_host
 g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
     -I rpg_monocular_pose_estimator_amd/csrc tests/host/wide_nn_host.cpp -o $WN && $WN || rc=1
 rm -rf "$(dirname $WN)"
+# the joint Gauss-Newton of a rig's cameras, k_rig_refine's logic (csrc/mpe_rig_gn.h) behind the tail helpers cut out of
+# mpe_k3.hip: a stand-alone program too (one camera with the identity extrinsic against k3_gauss_newton bit for bit,
+# rigs of up to 256 rows back to their true pose, the short problems)
+RG=$(mktemp -d)
+python -c "
+import rpg_monocular_pose_estimator_amd as mpe
+hip = mpe.device_source(); i = hip.index('struct T34 {')
+open('$RG/k3_extract.inc', 'w').write(hip[i:hip.index('#define K3_GROUP', i)])" && \
+g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+    -DRIG_GN_HOST_MAIN -I $RG -I tests/host/stub -I rpg_monocular_pose_estimator_amd/csrc tests/host/rig_gn_host.cpp \
+    -o $RG/rig_gn_host && $RG/rig_gn_host || rc=1
+rm -rf "$RG"
 exit $rc
