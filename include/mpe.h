@@ -794,6 +794,61 @@ int mpe_rig_fuse_trackers(mpe_tracker* const* trackers, int n, const double* T_c
 int mpe_rig_seed_trackers(mpe_tracker* const* trackers, int n, const double* T_cam_rig, const int* seed,
                           const double rig_pose[16], double time, const double* rig_prev_pose, double prev_time);
 
+/* ---- calibrating the extrinsics of a rig from the body it tracks (a bundle adjustment on the device) ----
+ * A recorded sequence of ONE body in front of the rig: view f (a time step) holds the rows [view_begin[f],
+ * view_begin[f+1]) of row_camera / row_marker_xyz (x 3) / row_uv (x 2, undistorted pixels), in any camera order, at most
+ * 256 of them.  The unknowns are a left twist on the pose T_f (rig <- marker frame) of every used view and a left twist
+ * on the extrinsic E_c (camera <- rig) of every camera but reference_camera, which keeps its extrinsic (the gauge); the
+ * residual is mpe_rig_optimise_pose_batch's, e = uv - project(K_c, E_c T_f p).  Plain Gauss-Newton with a Schur
+ * complement over the view poses, unpivoted LDL^T, every sum in row order / view order by one lane (no atomics: the
+ * same bits from run to run); stop when the largest |component| of all twists of an iteration is <= step_tolerance, or
+ * after max_iterations.
+ * Which rows take part: a view is used when it has >= 3 rows of >= 2 distinct cameras and its cameras are linked to the
+ * reference camera through such views; a camera that is not (or has no rows) is HELD — its extrinsic comes back as
+ * given, its rows are dropped; the poses of unused views come back as given.  Rank deficiency beyond these rules is the
+ * caller's concern.
+ * cameras: K and the START extrinsics; T_view_init: n_views x 16 start poses (mpe_rig_calibration_start makes both from
+ * per-camera poses).  T_cam_rig_out: n_cameras x 16; T_view_out (optional): n_views x 16; cov_out (optional): n_cameras
+ * x 36, the 6 x 6 diagonal block of the inverse of the reduced system of the last iteration — the marginal covariance
+ * of the camera's left twist for unit pixel noise, zero for the reference camera and held cameras; view_used
+ * (optional): n_views flags; report: status MPE_FRAME_POSE / MPE_FRAME_NO_POSE, iterations, views and rows used,
+ * rms = sqrt(mean e^2) over the residual components of the used rows at the start values and at the final values,
+ * last_step, camera_state (0 reference, 1 calibrated, 2 held) and camera_rows (rows used) per camera.
+ * Returns 1 calibrated; 0 not (no used view, or a non-finite output: status MPE_FRAME_NO_POSE, every extrinsic and view
+ * pose comes back as given, cov_out zero); before any device work MPE_ERR_ARG (a null pointer, n_cameras outside 1 ..
+ * 16, n_views < 0, a camera index outside the rig, a negative or decreasing view_begin, reference_camera outside the
+ * rig, max_iterations < 1, step_tolerance not positive, a submission of the handle that is not collected yet) or
+ * MPE_ERR_UNSUPPORTED (a view of more than 256 rows).  options == NULL: the defaults.  Any number of views per call:
+ * the views' records are worked through in chunks (set "rig_ba_record_kb": their device buffer at most, 0 = 65536).
+ * set "rig_ba_profile" 1: every launch of a call is bracketed by events; get "rig_ba_us_linearise" / "_reduce" /
+ * "_solve" / "_update" / "_finish" / "_covariance" (device time of the last call per step, microseconds) and
+ * "rig_ba_launches". */
+typedef struct mpe_rig_calibration_options {
+  int reference_camera; /* 0 */
+  int max_iterations;   /* 50 */
+  double step_tolerance; /* 1e-10 */
+} mpe_rig_calibration_options;
+void mpe_rig_calibration_default_options(mpe_rig_calibration_options* o);
+typedef struct mpe_rig_calibration_report {
+  int status, iterations, views_used, rows_used;
+  double rms_before, rms_after, last_step;
+  int camera_state[MPE_RIG_MAX_CAMERAS], camera_rows[MPE_RIG_MAX_CAMERAS];
+} mpe_rig_calibration_report;
+int mpe_rig_calibrate(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const int* view_begin,
+                      const int* row_camera, const double* row_marker_xyz, const double* row_uv, int n_views,
+                      const double* T_view_init, const mpe_rig_calibration_options* options, double* T_cam_rig_out,
+                      double* T_view_out, double* cov_out, int* view_used, mpe_rig_calibration_report* report);
+
+/* Start values for mpe_rig_calibrate from per-camera poses (what a lock-step call returns) — host only.  camera_pose:
+ * n_views x n_cameras x 16, camera <- marker frame; updated: n_views x n_cameras flags (a pose counts when non-zero).
+ * E_ref = I; breadth first from reference_camera over the views in order, camera c is linked through the first view in
+ * which c and an already linked c' both updated: E_c = P_cf P_c'f^-1 E_c' (an unlinked camera gets the identity,
+ * camera_linked[c] = 0).  T_f = E_c^-1 P_cf of the lowest linked camera that updated in f, the identity if none did.
+ * T_cam_rig_out: n_cameras x 16; T_view_out: n_views x 16; camera_linked (optional): n_cameras.  Returns the number of
+ * linked cameras (the reference camera included), or MPE_ERR_ARG. */
+int mpe_rig_calibration_start(const double* camera_pose, const int* updated, int n_views, int n_cameras,
+                              int reference_camera, double* T_cam_rig_out, double* T_view_out, int* camera_linked);
+
 /* Stage-level batch entry points (used by the parity tests at every stage boundary). */
 /* detection only (a1): dets is a HOST array of n_frames records */
 int mpe_detect_batch(mpe_handle* h, const uint8_t* frames, int n_frames, int rows, int cols,

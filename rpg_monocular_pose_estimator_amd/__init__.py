@@ -13,7 +13,9 @@ from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYP
                       tracker_estimate_batch, tracker_run_sequences_batch, tracker_estimate_batch_mixed,
                       tracker_run_sequences_batch_mixed, PinnedFrames, tracker_estimate_batch_device,
                       tracker_run_sequences_batch_device, ImageFormat, tracker_estimate_batch_formats,
-                      tracker_run_sequences_batch_formats, Rig, MpeRigCamera, RIG_MAX_CAMERAS)
+                      tracker_run_sequences_batch_formats, Rig, MpeRigCamera, RIG_MAX_CAMERAS,
+                      RigCalibrator, rig_calibration_start,
+                      MpeRigCalibrationOptions, MpeRigCalibrationReport)
 from .pose_estimator import PoseEstimator  # noqa: F401
 
 __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE", "DETECTIONS_DTYPE",
@@ -24,4 +26,6 @@ __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE"
            "shard_bounds", "estimate_batch_multi", "estimate_batch_multi_device_gather", "ENCODINGS", "tracker_estimate_batch", "tracker_run_sequences_batch", "tracker_estimate_batch_mixed",
            "tracker_run_sequences_batch_mixed", "PinnedFrames", "tracker_estimate_batch_device",
            "tracker_run_sequences_batch_device", "ImageFormat", "tracker_estimate_batch_formats",
-           "tracker_run_sequences_batch_formats", "Rig", "MpeRigCamera", "RIG_MAX_CAMERAS"]
+           "tracker_run_sequences_batch_formats", "Rig", "MpeRigCamera", "RIG_MAX_CAMERAS", "RigCalibrator",
+           "rig_calibration_start", "MpeRigCalibrationOptions",
+           "MpeRigCalibrationReport"]

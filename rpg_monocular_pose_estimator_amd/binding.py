@@ -59,6 +59,16 @@ class MpeRigCamera(C.Structure):  # mpe_rig_camera
     _fields_ = [("K", C.c_double * 9), ("T_cam_rig", C.c_double * 16)]
 
 
+class MpeRigCalibrationOptions(C.Structure):  # mpe_rig_calibration_options
+    _fields_ = [("reference_camera", C.c_int), ("max_iterations", C.c_int), ("step_tolerance", C.c_double)]
+
+
+class MpeRigCalibrationReport(C.Structure):  # mpe_rig_calibration_report
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("views_used", C.c_int), ("rows_used", C.c_int),
+                ("rms_before", C.c_double), ("rms_after", C.c_double), ("last_step", C.c_double),
+                ("camera_state", C.c_int * RIG_MAX_CAMERAS), ("camera_rows", C.c_int * RIG_MAX_CAMERAS)]
+
+
 RESULT_DTYPE = np.dtype([("T", "f8", (16,)), ("cov", "f8", (36,)), ("status", "i4"), ("n_det", "i4"),
                          ("n_corr", "i4"), ("gn_iterations", "i4")])
 DETECTIONS_DTYPE = np.dtype([("n", "i4"), ("status", "i4"), ("undist_xy", "f8", (2 * MAX_DETECTIONS,)),
@@ -115,7 +125,8 @@ def source_fingerprint():
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
                                   "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
-                                  "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig.cpp"):
+                                  "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
+                                  "mpe_rig_ba_plan.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -261,6 +272,12 @@ def load_library():
     lib.mpe_rig_optimise_pose_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, dp, dp, C.c_int, dp, C.c_void_p]
     lib.mpe_rig_fuse_trackers.argtypes = [hp, C.c_int, dp, ip, C.c_void_p, ip]
     lib.mpe_rig_seed_trackers.argtypes = [hp, C.c_int, dp, ip, dp, C.c_double, dp, C.c_double]
+    # the extrinsics of a rig calibrated from the body it tracks
+    lib.mpe_rig_calibration_default_options.argtypes = [C.POINTER(MpeRigCalibrationOptions)]
+    lib.mpe_rig_calibration_default_options.restype = None
+    lib.mpe_rig_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, dp, dp, C.c_int, dp,
+                                      C.POINTER(MpeRigCalibrationOptions), dp, dp, dp, ip, C.POINTER(MpeRigCalibrationReport)]
+    lib.mpe_rig_calibration_start.argtypes = [dp, ip, C.c_int, C.c_int, C.c_int, dp, dp, ip]
     lib.mpe_tracker_get_correspondences.argtypes = [C.c_void_p, up, C.c_int]
     lib.mpe_tracker_get_image_points.argtypes = [C.c_void_p, dp, C.c_int]
     _lib = lib
@@ -994,6 +1011,31 @@ class Handle:
         self._check(rc, "mpe_rig_optimise_pose_batch")
         return rec
 
+    def rig_calibrate(self, cameras, views, T_views, reference_camera=0, max_iterations=50, step_tolerance=1e-10):
+        """mpe_rig_calibrate: the extrinsics of a rig from a recorded sequence of ONE body (a bundle adjustment on the
+        device over the extrinsics of all cameras but reference_camera and one pose per view).  cameras: a list of
+        (K 3x3, T_cam_rig 4x4 camera <- rig, the START value); views: a list of row lists, a row = (camera index, marker
+        xyz, undistorted pixel uv), any camera order; T_views: (n, 4, 4) start poses, rig <- marker frame.
+        -> dict(T_cam_rig (n_cam, 4, 4), T_views (n, 4, 4), cov (n_cam, 6, 6), view_used (n) bool, report dict,
+        ok): ok False (report status 1) hands every extrinsic and pose back as given."""
+        cams, begin, cam, xyz, uv = pack_rig_views(cameras, views)
+        n, n_cam = len(views), len(cameras)
+        T0 = _f64(T_views).reshape(-1, 16)
+        assert len(T0) == n
+        opt = MpeRigCalibrationOptions(int(reference_camera), int(max_iterations), float(step_tolerance))
+        E = np.zeros((max(n_cam, 1), 4, 4))
+        T = np.zeros((max(n, 1), 4, 4))
+        cov = np.zeros((max(n_cam, 1), 6, 6))
+        used = np.zeros(max(n, 1), np.int32)
+        rep = MpeRigCalibrationReport()
+        ip = C.POINTER(C.c_int)
+        rc = self._lib.mpe_rig_calibrate(self._h, cams, n_cam, begin.ctypes.data_as(ip), cam.ctypes.data_as(ip), _dp(xyz),
+                                         _dp(uv), n, _dp(T0), C.byref(opt), _dp(E), _dp(T), _dp(cov), used.ctypes.data_as(ip),
+                                         C.byref(rep))
+        self._check(min(rc, 0), "mpe_rig_calibrate")
+        return dict(T_cam_rig=E[:n_cam], T_views=T[:n], cov=cov[:n_cam], view_used=used[:n].astype(bool),
+                    report=rig_calibration_report_dict(rep, n_cam), ok=rc == 1)
+
     # ---- one tracked frame: findLeds(ROI) + findCorrespondences + checkCorrespondences + optimisePose ----
     def track_step(self, img, roi, params, K, D, markers, predicted_px):
         img = np.ascontiguousarray(img, np.uint8)
@@ -1297,6 +1339,7 @@ class Tracker:
         markers = _f64(markers).reshape(-1, 3)
         K = _f64(K).reshape(9)
         D = _f64(D).reshape(-1)
+        self.markers, self.K = markers.copy(), K.reshape(3, 3).copy()
         handle._check(self._lib.mpe_tracker_set_markers(self._t, _dp(markers), len(markers)), "mpe_tracker_set_markers")
         handle._check(self._lib.mpe_tracker_set_camera(self._t, _dp(K), _dp(D), len(D)), "mpe_tracker_set_camera")
         self.set_params(params)
@@ -1419,3 +1462,96 @@ class Rig:
             self.seed(~upd, rig["T"][0], t, None if prev is None else prev[0], 0.0 if prev is None else prev[1])
         self._prev = (rig["T"][0].copy(), t) if fused else None
         return rec, info, upd, rig, fused
+
+
+def pack_rig_views(cameras, views):
+    """The arrays mpe_rig_calibrate takes: cameras [(K, T_cam_rig)], views = row lists of (camera, marker xyz, pixel uv)
+    -> (mpe_rig_camera array, view_begin, row_camera, row_marker_xyz, row_uv)."""
+    cams = (MpeRigCamera * max(1, len(cameras)))()
+    for c, (K, E) in zip(cams, cameras):
+        c.K[:] = _f64(K).reshape(9)
+        c.T_cam_rig[:] = _f64(E).reshape(16)
+    begin = np.zeros(len(views) + 1, np.int32)
+    begin[1:] = np.cumsum([len(rows) for rows in views])
+    flat = [r for rows in views for r in rows]
+    cam = np.ascontiguousarray([r[0] for r in flat], np.int32).reshape(-1)
+    xyz = _f64([r[1] for r in flat]).reshape(-1, 3)
+    uv = _f64([r[2] for r in flat]).reshape(-1, 2)
+    return cams, begin, cam, xyz, uv
+
+
+def rig_calibration_report_dict(rep, n_cam):
+    return dict(status=rep.status, iterations=rep.iterations, views_used=rep.views_used, rows_used=rep.rows_used,
+                rms_before=rep.rms_before, rms_after=rep.rms_after, last_step=rep.last_step,
+                camera_state=list(rep.camera_state[:n_cam]), camera_rows=list(rep.camera_rows[:n_cam]))
+
+
+def rig_calibration_start(camera_pose, updated, reference_camera=0):
+    """mpe_rig_calibration_start (host only): start values for Handle.rig_calibrate from per-camera poses.  camera_pose:
+    (n_views, n_cam, 4, 4), camera <- marker frame; updated: (n_views, n_cam).  -> (T_cam_rig (n_cam, 4, 4), T_views
+    (n_views, 4, 4), linked (n_cam) bool): E_ref = I, the others chained through the first view they share with a
+    linked camera."""
+    lib = load_library()
+    P = _f64(camera_pose)
+    n_views, n_cam = P.shape[0], P.shape[1]
+    upd = np.ascontiguousarray(updated, np.int32).reshape(n_views, n_cam)
+    E = np.zeros((n_cam, 4, 4))
+    T = np.zeros((max(n_views, 1), 4, 4))
+    linked = np.zeros(n_cam, np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = lib.mpe_rig_calibration_start(_dp(P), upd.ctypes.data_as(ip), n_views, n_cam, int(reference_camera), _dp(E), _dp(T),
+                                       linked.ctypes.data_as(ip))
+    if rc < 0:
+        raise MpeError("mpe_rig_calibration_start failed (%d)" % rc)
+    return E, T[:n_views], linked.astype(bool)
+
+
+class RigCalibrator:
+    """Calibrates the extrinsics of a rig from the body it tracks: step() drives the lock-step entry of the trackers (one
+    per camera, one handle, one marker set) as Rig.step does and keeps, for every tracker that updated, its pose and its
+    rows (correspondences() over image_points() and the markers); solve() makes start values from the stored poses
+    (rig_calibration_start) and runs Handle.rig_calibrate over the stored rows; rig() is a Rig with the result."""
+
+    def __init__(self, handle, trackers, reference_camera=0):
+        self.handle = handle
+        self.trackers = list(trackers)
+        self.reference_camera = int(reference_camera)
+        self.views, self.poses, self.updated = [], [], []
+        self.result = None
+
+    def step(self, imgs, times, formats=None):
+        """One time step -> (records (N), info (N, 8), updated (N)): the lock-step entry's, unchanged."""
+        same = formats is None and not _is_torch(imgs[0]) and len({(np.shape(im), np.asarray(im).strides[0]) for im in imgs}) == 1
+        if same:
+            rec, info, upd = tracker_estimate_batch_mixed(self.trackers, imgs, times)
+        else:
+            rec, info, upd = tracker_estimate_batch_formats(self.trackers, imgs, times, formats)
+        rows = []
+        for c, t in enumerate(self.trackers):
+            if not upd[c]:
+                continue
+            xy = t.image_points()
+            rows += [(c, t.markers[m - 1].copy(), xy[j - 1].copy()) for m, j in t.correspondences()]
+        self.views.append(rows)
+        self.poses.append(rec["T"].reshape(len(self.trackers), 4, 4).copy())
+        self.updated.append(np.asarray(upd, bool).copy())
+        return rec, info, upd
+
+    def start(self):
+        """-> (T_cam_rig, T_views, linked) of rig_calibration_start over the stored poses."""
+        return rig_calibration_start(np.array(self.poses), np.array(self.updated), self.reference_camera)
+
+    def solve(self, max_iterations=50, step_tolerance=1e-10):
+        """-> Handle.rig_calibrate's dict (kept as self.result), with the start values as "start"."""
+        E0, T0, linked = self.start()
+        cameras = [(t.K, E0[c]) for c, t in enumerate(self.trackers)]
+        out = self.handle.rig_calibrate(cameras, self.views, T0, self.reference_camera, max_iterations, step_tolerance)
+        out["start"] = dict(T_cam_rig=E0, T_views=T0, linked=linked)
+        self.result = out
+        return out
+
+    def rig(self):
+        """A Rig over the same trackers with the calibrated extrinsics."""
+        if self.result is None or not self.result["ok"]:
+            raise MpeError("RigCalibrator.rig: no calibration (call solve() first; it must succeed)")
+        return Rig(self.handle, self.trackers, self.result["T_cam_rig"])

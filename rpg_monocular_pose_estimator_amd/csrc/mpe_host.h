@@ -122,6 +122,15 @@ struct mpe_handle {
   long long wide_frames = 0;
   long long wide_track_submits = 0;  // get "wide_track_submits": submissions of mpe_track_step_batch_wide
   int wide_block_cap = 0;
+  // option "rig_ba_record_kb": KiB of device memory the view records of mpe_rig_calibrate may take at a time (the views
+  // are worked through in chunks of that size); 0 = 65536
+  int rig_ba_record_kb = 0;
+  // option "rig_ba_profile" = 1: mpe_rig_calibrate brackets every launch with a pair of events and leaves, per step
+  // (MPE_RIG_BA_LINEARISE .. _COVARIANCE), the summed device time and the number of launches of the last call: get
+  // "rig_ba_us_linearise" / _reduce / _solve / _update / _finish / _covariance, "rig_ba_launches"
+  int rig_ba_profile = 0;
+  double rig_ba_ms[6] = {0, 0, 0, 0, 0, 0};
+  int rig_ba_launches = 0;
   int pending_track_n = 0;            // a batch submission without its _collect yet: streams in flight
   uint8_t* pending_track_rec = nullptr;
   // How many detections the frames of a pipelined call are expected to carry: picks the voting-kernel variant (from 9

@@ -207,6 +207,12 @@ hipError_t launch_k_nn_wide(const mpe_detections_wide* dets, const double* pred,
 hipError_t launch_k_rig_refine(const mpe_rig_camera* cams, int n_cam, const int* row_begin, const int* row_cam,
                                const double* row_xyz, const double* row_uv, const double* T_init, int n_problems,
                                mpe_result* out, hipStream_t s);
+// the steps of mpe_rig_calibrate (mpe_rig_ba.h), each a launch of its own: linearise / update over the used views
+// [first, first + count) of one chunk, reduce over the same with flag = 1 when the sums start anew, finish with flag = 1
+// when the cameras take their step; solve and covariance take neither.  The table holds device pointers.
+#include "mpe_rig_ba_dev.h"
+enum { MPE_RIG_BA_LINEARISE = 0, MPE_RIG_BA_REDUCE, MPE_RIG_BA_SOLVE, MPE_RIG_BA_UPDATE, MPE_RIG_BA_FINISH, MPE_RIG_BA_COVARIANCE };
+hipError_t launch_k_rig_ba(int step, const RigBaDev& d, int first, int count, int flag, hipStream_t s);
 hipError_t launch_k2_vote_wide(const mpe_detections_wide* dets, const SolveParams& sp, const BruteBlock* blocks,
                                int n_blocks, uint32_t* hist, hipStream_t s);
 hipError_t launch_k3_peel_wide(const mpe_detections_wide* dets, const uint32_t* hist, int n_items, int n_markers,

@@ -1346,6 +1346,76 @@ hipError_t launch_k_rig_refine(const mpe_rig_camera* cams, int n_cam, const int*
   return hipGetLastError();
 }
 
+// The extrinsics of a rig calibrated from the body it tracks (mpe_rig_calibrate): the steps of mpe_rig_ba.h, each a
+// launch of its own on the caller's stream — kernel boundaries order them, no flag crosses a block.  Waves of 64:
+// linearise one block per used view of the chunk, reduce one block per 6 x 6 block (i <= j) of the free cameras, solve
+// and finish one block, update one lane per view, covariance one block per free camera.  The host has checked the row
+// counts and camera indices and sized the records (rig_ba_plan).
+#include "mpe_rig_ba.h"
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_ba_linearise(RigBaDev d, int first, int count) {
+  __shared__ RigBaLinLds s_lin;
+  if ((int)blockIdx.x >= count) return;  // (block-uniform)
+  rig_ba_linearise(s_lin, d, first + (int)blockIdx.x, first);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_ba_reduce(RigBaDev d, int first, int count, int restart) {
+  __shared__ RigBaRedLds s_red;
+  int i = 0, p = (int)blockIdx.x;  // block p of the upper triangle, row by row
+  while (p >= d.n_free - i) {
+    p -= d.n_free - i;
+    ++i;
+  }
+  if (i >= d.n_free) return;
+  rig_ba_reduce(s_red, d, i, i + p, first, count, restart);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_ba_solve(RigBaDev d) {
+  __shared__ RigBaSolveLds s_solve;
+  rig_ba_solve(s_solve, d);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_ba_covariance(RigBaDev d) {
+  __shared__ RigBaSolveLds s_solve;
+  if ((int)blockIdx.x >= d.n_free) return;
+  rig_ba_covariance(s_solve, d, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_ba_update(RigBaDev d, int first, int count) {
+  const int v = (int)(blockIdx.x * MPE_RIG_LANES + threadIdx.x);
+  if (v < count) rig_ba_update_view(d, first + v, first);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_ba_finish(RigBaDev d, int apply) {
+  __shared__ RigBaFinLds s_fin;
+  rig_ba_finish(s_fin, d, apply);
+}
+hipError_t launch_k_rig_ba(int step, const RigBaDev& d, int first, int count, int flag, hipStream_t s) {
+  const dim3 wave(MPE_RIG_LANES);
+  if (d.n_free < 1 || d.n_free > MPE_RIG_BA_MAX_FREE || d.n_cam > MPE_RIG_MAX_CAMERAS || d.n_views < 1 || first < 0 ||
+      count < 0 || first + count > d.n_views)
+    return hipErrorInvalidValue;
+  switch (step) {
+    case MPE_RIG_BA_LINEARISE:
+      if (count) hipLaunchKernelGGL(k_rig_ba_linearise, dim3((unsigned)count), wave, 0, s, d, first, count);
+      break;
+    case MPE_RIG_BA_REDUCE:
+      hipLaunchKernelGGL(k_rig_ba_reduce, dim3((unsigned)(d.n_free * (d.n_free + 1) / 2)), wave, 0, s, d, first, count, flag);
+      break;
+    case MPE_RIG_BA_SOLVE:
+      hipLaunchKernelGGL(k_rig_ba_solve, dim3(1), wave, 0, s, d);
+      break;
+    case MPE_RIG_BA_UPDATE:
+      if (count)
+        hipLaunchKernelGGL(k_rig_ba_update, dim3((unsigned)((count + MPE_RIG_LANES - 1) / MPE_RIG_LANES)), wave, 0, s, d, first,
+                           count);
+      break;
+    case MPE_RIG_BA_FINISH:
+      hipLaunchKernelGGL(k_rig_ba_finish, dim3(1), wave, 0, s, d, flag);
+      break;
+    case MPE_RIG_BA_COVARIANCE:
+      hipLaunchKernelGGL(k_rig_ba_covariance, dim3((unsigned)d.n_free), wave, 0, s, d);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_k3_tail(const mpe_detections* dets, const uint32_t* hist, int n_frames, const SolveParams& sp,
                           mpe_result* results, uint32_t* corr_out, const uint32_t* corr_in, const double* nn_pred,
                           double nn_tol, void* mid_buf, hipStream_t s, int mode) {

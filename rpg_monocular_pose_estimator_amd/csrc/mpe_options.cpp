@@ -289,6 +289,16 @@ int mpe_get_option(mpe_handle* h, const char* name, int* value) {
   else if (n == "wide_frames") *value = (int)h->wide_frames;
   else if (n == "wide_track_submits") *value = (int)h->wide_track_submits;
   else if (n == "wide_block_cap") *value = h->wide_block_cap;
+  else if (n == "rig_ba_record_kb") *value = h->rig_ba_record_kb;
+  else if (n == "rig_ba_profile") *value = h->rig_ba_profile;
+  else if (n == "rig_ba_launches") *value = h->rig_ba_launches;
+  else if (n.rfind("rig_ba_us_", 0) == 0) {
+    static const char* const steps[6] = {"linearise", "reduce", "solve", "update", "finish", "covariance"};
+    int k = 0;
+    while (k < 6 && n.substr(10) != steps[k]) ++k;
+    if (k == 6) return fail(h, MPE_ERR_ARG, "unknown option");
+    *value = (int)(h->rig_ba_ms[k] * 1e3 + 0.5);
+  }
   else if (n == "track_ns_pack") *value = (int)(h->track_ns[0] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_enqueue") *value = (int)(h->track_ns[1] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_wait") *value = (int)(h->track_ns[2] / std::max(1LL, h->track_steps));
@@ -471,6 +481,15 @@ int mpe_set_option(mpe_handle* h, const char* name, int value) {
   if (!std::strcmp(name, "wide_block_cap")) {  // tests: blocks per set of the wide voting launch at most (0 = automatic)
     if (value < 0) return fail(h, MPE_ERR_ARG, "wide_block_cap must be >= 0");
     h->wide_block_cap = value;
+    return MPE_OK;
+  }
+  if (!std::strcmp(name, "rig_ba_profile")) {  // mpe_rig_calibrate times its launches per step (get "rig_ba_us_*")
+    h->rig_ba_profile = value ? 1 : 0;
+    return MPE_OK;
+  }
+  if (!std::strcmp(name, "rig_ba_record_kb")) {  // KiB the view records of mpe_rig_calibrate take at a time (0 = 65536)
+    if (value < 0) return fail(h, MPE_ERR_ARG, "rig_ba_record_kb must be >= 0");
+    h->rig_ba_record_kb = value;
     return MPE_OK;
   }
   if (!std::strcmp(name, "vote_arith")) {

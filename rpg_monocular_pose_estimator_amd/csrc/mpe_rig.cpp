@@ -2,11 +2,100 @@
 // pose.  mpe_rig_optimise_pose_batch — the joint Gauss-Newton (k_rig_refine, mpe_k3.hip; logic in mpe_rig_gn.h) over
 // rows that bring their own camera: one input copy, one launch, one copy back.  What works on the trackers of a rig
 // (mpe_rig_fuse_trackers, mpe_rig_seed_trackers) is in mpe_tracker.cpp, beside the state it reads and sets, and comes
-// here through the public entry.
+// here through the public entry.  mpe_rig_calibrate — the extrinsics of a rig from a recorded sequence of the body: which
+// rows take part and the iteration are mpe_rig_ba_plan.h (shared with the CPU tier), the steps are the k_rig_ba_* kernels
+// (mpe_k3.hip; logic in mpe_rig_ba.h), one launch each on the handle's stream; the host reads two doubles per iteration.
+// mpe_rig_calibration_start — start values from per-camera poses, host only.
 #include "mpe_host.h"
+#include "mpe_rig_ba_plan.h"
 
 namespace {
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the steps of rig_ba_iterate as launches on the handle's stream
+struct RigBaLaunches {
+  mpe_handle* h;
+  RigBaDev d;
+  double* host_out;  // pinned: where finish's two doubles land
+  hipError_t err = hipSuccess;
+  struct Timed {
+    int step;
+    hipEvent_t a, b;
+  };
+  std::vector<Timed> timed;  // option "rig_ba_profile": a pair of events around every launch
+  int run(int step, int first, int count, int flag) {
+    Timed t = {step, nullptr, nullptr};
+    const bool prof = h->rig_ba_profile != 0;
+    if (prof) {  // (whatever was created is in `timed` before anything can fail: read_out gives it back)
+      if ((err = hipEventCreate(&t.a)) == hipSuccess) err = hipEventCreate(&t.b);
+      timed.push_back(t);
+      if (err != hipSuccess || (err = hipEventRecord(t.a, h->stream)) != hipSuccess) return 1;
+    }
+    err = launch_k_rig_ba(step, d, first, count, flag, h->stream);
+    if (prof && err == hipSuccess) err = hipEventRecord(t.b, h->stream);
+    return err == hipSuccess ? 0 : 1;
+  }
+  // behind the last synchronisation of the call: the sums per step into the handle, the events given back
+  void read_out() {
+    if (!timed.empty()) {
+      for (double& v : h->rig_ba_ms) v = 0;
+      h->rig_ba_launches = (int)timed.size();
+    }
+    for (const Timed& t : timed) {
+      float ms = 0;
+      if (t.a && t.b && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) h->rig_ba_ms[t.step] += ms;
+      if (t.a) (void)hipEventDestroy(t.a);
+      if (t.b) (void)hipEventDestroy(t.b);
+    }
+    timed.clear();
+  }
+  ~RigBaLaunches() { read_out(); }
+  int linearise(int first, int count) { return run(MPE_RIG_BA_LINEARISE, first, count, 0); }
+  int reduce(int first, int count, bool restart) { return run(MPE_RIG_BA_REDUCE, first, count, restart ? 1 : 0); }
+  int solve() { return run(MPE_RIG_BA_SOLVE, 0, 0, 0); }
+  int update(int first, int count) { return run(MPE_RIG_BA_UPDATE, first, count, 0); }
+  int covariance() { return run(MPE_RIG_BA_COVARIANCE, 0, 0, 0); }
+  int finish(int apply, double out2[2]) {
+    if (run(MPE_RIG_BA_FINISH, 0, 0, apply)) return 1;
+    if ((err = hipMemcpyAsync(host_out, d.out, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream)) != hipSuccess) return 1;
+    if ((err = hipStreamSynchronize(h->stream)) != hipSuccess) return 1;
+    out2[0] = host_out[0];
+    out2[1] = host_out[1];
+    return 0;
+  }
+};
+
+struct M44 {
+  double a[16];
+};
+M44 m44_from(const double* p) {
+  M44 m;
+  std::memcpy(m.a, p, sizeof(m.a));
+  return m;
+}
+M44 m44_identity() {
+  M44 m = {};
+  for (int i = 0; i < 16; i += 5) m.a[i] = 1.0;
+  return m;
+}
+M44 m44_mul(const M44& x, const M44& y) {
+  M44 r;
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      double s = 0;
+      for (int k = 0; k < 4; ++k) s += x.a[4 * i + k] * y.a[4 * k + j];
+      r.a[4 * i + j] = s;
+    }
+  return r;
+}
+M44 m44_rigid_inverse(const M44& x) {  // [R | t]^-1 = [R^T | -R^T t]
+  M44 r = m44_identity();
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) r.a[4 * i + j] = x.a[4 * j + i];
+    r.a[4 * i + 3] = -(x.a[i] * x.a[3] + x.a[4 + i] * x.a[7] + x.a[8 + i] * x.a[11]);
+  }
+  return r;
+}
 }  // namespace
 
 extern "C" {
@@ -67,6 +156,176 @@ int mpe_rig_optimise_pose_batch(mpe_handle* h, const mpe_rig_camera* cameras, in
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   std::memcpy(out, mb + back_off, back_bytes);
   return MPE_OK;
+}
+
+void mpe_rig_calibration_default_options(mpe_rig_calibration_options* o) {
+  if (!o) return;
+  o->reference_camera = 0;
+  o->max_iterations = 50;
+  o->step_tolerance = 1e-10;
+}
+
+int mpe_rig_calibrate(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const int* view_begin,
+                      const int* row_camera, const double* row_marker_xyz, const double* row_uv, int n_views,
+                      const double* T_view_init, const mpe_rig_calibration_options* options, double* T_cam_rig_out,
+                      double* T_view_out, double* cov_out, int* view_used, mpe_rig_calibration_report* report) {
+  if (!h || n_views < 0) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (!cameras) return fail(h, MPE_ERR_ARG, "cameras is null");
+  if (!view_begin) return fail(h, MPE_ERR_ARG, "view_begin is null");
+  if (!T_cam_rig_out) return fail(h, MPE_ERR_ARG, "T_cam_rig_out is null");
+  if (!report) return fail(h, MPE_ERR_ARG, "report is null");
+  if (n_views > 0 && !T_view_init) return fail(h, MPE_ERR_ARG, "T_view_init is null");
+  if (n_cameras < 1 || n_cameras > MPE_RIG_MAX_CAMERAS) return fail(h, MPE_ERR_ARG, "n_cameras outside 1 .. MPE_RIG_MAX_CAMERAS");
+  mpe_rig_calibration_options opt;
+  mpe_rig_calibration_default_options(&opt);
+  if (options) opt = *options;
+  if (opt.reference_camera < 0 || opt.reference_camera >= n_cameras) return fail(h, MPE_ERR_ARG, "reference_camera outside the rig");
+  if (opt.max_iterations < 1) return fail(h, MPE_ERR_ARG, "max_iterations must be >= 1");
+  if (!(opt.step_tolerance > 0)) return fail(h, MPE_ERR_ARG, "step_tolerance must be positive");
+  if (view_begin[0] < 0) return fail(h, MPE_ERR_ARG, "view_begin is negative");
+  for (int f = 0; f < n_views; ++f) {
+    if (view_begin[f + 1] < view_begin[f]) return fail(h, MPE_ERR_ARG, "view_begin decreases");
+    if (view_begin[f + 1] - view_begin[f] > MPE_RIG_MAX_CAMERAS * MPE_MAX_MARKERS)
+      return fail(h, MPE_ERR_UNSUPPORTED, "more than MPE_RIG_MAX_CAMERAS * MPE_MAX_MARKERS rows in a view");
+  }
+  const int r0 = view_begin[0], r1 = view_begin[n_views];
+  if (r1 > r0 && (!row_camera || !row_marker_xyz || !row_uv)) return fail(h, MPE_ERR_ARG, "a row array is null");
+  for (int j = r0; j < r1; ++j)
+    if (row_camera[j] < 0 || row_camera[j] >= n_cameras) return fail(h, MPE_ERR_ARG, "camera index outside the rig");
+  if (h->pending_track_n || h->submit_seq != h->collect_seq)
+    return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+
+  RigBaPlan P;
+  rig_ba_plan(n_cameras, opt.reference_camera, view_begin, row_camera, row_marker_xyz, row_uv, n_views, MPE_RIG_BA_HEAD,
+              MPE_RIG_BA_SLOT, P);
+  rig_ba_give_back(P, cameras, n_views, T_view_init, T_cam_rig_out, T_view_out, cov_out, view_used, report);
+  if (P.views_used == 0 || P.n_free == 0) return 0;
+
+  ENTER(h);
+  const int nv = P.views_used, nr = P.rows_used, nf = P.n_free;
+  // one block of device memory: [cameras | free index | view_begin | masks | record offsets | row cameras | marker xyz |
+  // pixels | view poses] from the host, then what the steps keep among themselves
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += up256(bytes);
+    return o;
+  };
+  const size_t o_cam = take((size_t)n_cameras * sizeof(mpe_rig_camera)), o_free = take(16 * sizeof(int)),
+               o_beg = take((size_t)(nv + 1) * sizeof(int)), o_mask = take((size_t)nv * sizeof(unsigned)),
+               o_cum = take((size_t)(nv + 1) * sizeof(long long)), o_rc = take((size_t)nr * sizeof(int)),
+               o_xyz = take((size_t)nr * 3 * sizeof(double)), o_uv = take((size_t)nr * 2 * sizeof(double)),
+               o_T = take((size_t)nv * 16 * sizeof(double));
+  const size_t in_bytes = off;
+  const size_t o_cov = take((size_t)nf * 36 * sizeof(double)), o_out = take(2 * sizeof(double));
+  const size_t back_end = off;  // [o_cam, in_bytes) and [o_cov, back_end) come back
+  const size_t o_sse = take((size_t)nv * sizeof(double)), o_step = take((size_t)nv * sizeof(double)),
+               o_S = take((size_t)(nf * (nf + 1) / 2) * 72 * sizeof(double)), o_r = take((size_t)nf * 12 * sizeof(double)),
+               o_L = take((size_t)MPE_RIG_BA_TRI * sizeof(double)), o_eta = take((size_t)MPE_RIG_BA_MAX_N * sizeof(double));
+  const size_t dev_bytes = off;
+  { const int rc = grow_mailbox(h, back_end); if (rc != MPE_OK) return rc; }
+  uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
+  std::memset(mb, 0, in_bytes);
+  std::memcpy(mb + o_cam, cameras, (size_t)n_cameras * sizeof(mpe_rig_camera));
+  std::memcpy(mb + o_free, P.cam_free, 16 * sizeof(int));
+  std::memcpy(mb + o_beg, P.view_begin.data(), (size_t)(nv + 1) * sizeof(int));
+  std::memcpy(mb + o_mask, P.view_mask.data(), (size_t)nv * sizeof(unsigned));
+  std::memcpy(mb + o_cum, P.view_cum.data(), (size_t)(nv + 1) * sizeof(long long));
+  std::memcpy(mb + o_rc, P.row_cam.data(), (size_t)nr * sizeof(int));
+  std::memcpy(mb + o_xyz, P.row_xyz.data(), (size_t)nr * 3 * sizeof(double));
+  std::memcpy(mb + o_uv, P.row_uv.data(), (size_t)nr * 2 * sizeof(double));
+  for (int v = 0; v < nv; ++v)
+    std::memcpy(mb + o_T + (size_t)v * 16 * sizeof(double), T_view_init + 16 * (size_t)P.view_of[(size_t)v], 16 * sizeof(double));
+  // the records of one chunk of views
+  const long long cap_doubles = (long long)(h->rig_ba_record_kb > 0 ? h->rig_ba_record_kb : 65536) * 1024 / 8;
+  const std::vector<std::pair<int, int>> chunks = rig_ba_chunks(P, cap_doubles);
+  long long rec_doubles = 0;
+  for (const auto& c : chunks)
+    rec_doubles = std::max(rec_doubles, P.view_cum[(size_t)(c.first + c.second)] - P.view_cum[(size_t)c.first]);
+  HIP_TRY(h, h->frames.reserve(dev_bytes));
+  HIP_TRY(h, h->scratch.reserve((size_t)rec_doubles * sizeof(double)));
+  uint8_t* dv = static_cast<uint8_t*>(h->frames.p);
+  HIP_TRY(h, hipMemcpyAsync(dv, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemsetAsync(dv + o_cov, 0, (size_t)nf * 36 * sizeof(double), h->stream));
+  RigBaLaunches B;
+  B.h = h;
+  B.host_out = reinterpret_cast<double*>(mb + o_out);
+  RigBaDev& d = B.d;
+  d.cams = reinterpret_cast<mpe_rig_camera*>(dv + o_cam);
+  d.cam_free = reinterpret_cast<const int*>(dv + o_free);
+  d.n_cam = n_cameras, d.n_free = nf, d.n_views = nv;
+  d.view_begin = reinterpret_cast<const int*>(dv + o_beg);
+  d.view_mask = reinterpret_cast<const unsigned*>(dv + o_mask);
+  d.view_cum = reinterpret_cast<const long long*>(dv + o_cum);
+  d.row_cam = reinterpret_cast<const int*>(dv + o_rc);
+  d.row_xyz = reinterpret_cast<const double*>(dv + o_xyz);
+  d.row_uv = reinterpret_cast<const double*>(dv + o_uv);
+  d.T_view = reinterpret_cast<double*>(dv + o_T);
+  d.rec = static_cast<double*>(h->scratch.p);
+  d.sse = reinterpret_cast<double*>(dv + o_sse);
+  d.step = reinterpret_cast<double*>(dv + o_step);
+  d.Sacc = reinterpret_cast<double*>(dv + o_S);
+  d.racc = reinterpret_cast<double*>(dv + o_r);
+  d.Lf = reinterpret_cast<double*>(dv + o_L);
+  d.eta = reinterpret_cast<double*>(dv + o_eta);
+  d.cov = reinterpret_cast<double*>(dv + o_cov);
+  d.out = reinterpret_cast<double*>(dv + o_out);
+  RigBaOutcome o;
+  if (rig_ba_iterate(B, chunks, opt.max_iterations, opt.step_tolerance, o)) return fail(h, MPE_ERR_HIP, "mpe_rig_calibrate", B.err);
+  HIP_TRY(h, hipMemcpyAsync(mb + o_cam, dv + o_cam, (size_t)n_cameras * sizeof(mpe_rig_camera), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(mb + o_T, dv + o_T, (size_t)nv * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(mb + o_cov, dv + o_cov, (size_t)nf * 36 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  B.read_out();
+  const mpe_rig_camera* cam_back = reinterpret_cast<const mpe_rig_camera*>(mb + o_cam);
+  const double* T_back = reinterpret_cast<const double*>(mb + o_T);
+  const double* cov_back = reinterpret_cast<const double*>(mb + o_cov);
+  return rig_ba_hand_out(P, o, cam_back, T_back, cov_back, T_cam_rig_out, T_view_out, cov_out, report);
+}
+
+int mpe_rig_calibration_start(const double* camera_pose, const int* updated, int n_views, int n_cameras,
+                              int reference_camera, double* T_cam_rig_out, double* T_view_out, int* camera_linked) {
+  if (!camera_pose || !updated || !T_cam_rig_out || !T_view_out || n_views < 0 || n_cameras < 1 ||
+      n_cameras > MPE_RIG_MAX_CAMERAS || reference_camera < 0 || reference_camera >= n_cameras)
+    return MPE_ERR_ARG;
+  std::vector<M44> E((size_t)n_cameras, m44_identity());
+  int round_of[MPE_RIG_MAX_CAMERAS];  // the round in which the camera was linked, -1 not yet
+  for (int c = 0; c < n_cameras; ++c) round_of[c] = -1;
+  round_of[reference_camera] = 0;
+  auto pose = [&](int f, int c) { return m44_from(camera_pose + 16 * ((size_t)f * n_cameras + c)); };
+  int n_linked = 1;
+  for (int round = 1; round <= n_cameras; ++round) {
+    bool any = false;
+    for (int f = 0; f < n_views; ++f) {
+      const int* u = updated + (size_t)f * n_cameras;
+      int via = -1;  // the lowest camera linked in an earlier round that updated in f
+      for (int c = 0; c < n_cameras && via < 0; ++c)
+        if (u[c] && round_of[c] >= 0 && round_of[c] < round) via = c;
+      if (via < 0) continue;
+      for (int c = 0; c < n_cameras; ++c)
+        if (u[c] && round_of[c] < 0) {
+          E[(size_t)c] = m44_mul(m44_mul(pose(f, c), m44_rigid_inverse(pose(f, via))), E[(size_t)via]);
+          round_of[c] = round;
+          ++n_linked;
+          any = true;
+        }
+    }
+    if (!any) break;
+  }
+  for (int c = 0; c < n_cameras; ++c) {
+    std::memcpy(T_cam_rig_out + 16 * (size_t)c, E[(size_t)c].a, 16 * sizeof(double));
+    if (camera_linked) camera_linked[c] = round_of[c] >= 0 ? 1 : 0;
+  }
+  for (int f = 0; f < n_views; ++f) {
+    M44 T = m44_identity();
+    for (int c = 0; c < n_cameras; ++c)
+      if (updated[(size_t)f * n_cameras + c] && round_of[c] >= 0) {
+        T = m44_mul(m44_rigid_inverse(E[(size_t)c]), pose(f, c));
+        break;
+      }
+    std::memcpy(T_view_out + 16 * (size_t)f, T.a, 16 * sizeof(double));
+  }
+  return n_linked;
 }
 
 }  // extern "C"

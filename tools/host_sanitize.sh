@@ -43,4 +43,16 @@ g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-saniti
     -DRIG_GN_HOST_MAIN -I $RG -I tests/host/stub -I rpg_monocular_pose_estimator_amd/csrc tests/host/rig_gn_host.cpp \
     -o $RG/rig_gn_host && $RG/rig_gn_host || rc=1
 rm -rf "$RG"
+# the steps of the rig calibration, the k_rig_ba_* kernels' logic (csrc/mpe_rig_ba.h) behind mpe_rig_gn.h and the same cut
+# of mpe_k3.hip, driven by the library's own row rules and iteration (csrc/mpe_rig_ba_plan.h): a stand-alone program too
+# (exact-pixel rigs of 2 .. 16 cameras back to their extrinsics, again in chunks of one view bit for bit, the row rules)
+RB=$(mktemp -d)
+python -c "
+import rpg_monocular_pose_estimator_amd as mpe
+hip = mpe.device_source(); i = hip.index('struct T34 {')
+open('$RB/k3_extract.inc', 'w').write(hip[i:hip.index('#define K3_GROUP', i)])" && \
+g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+    -DRIG_BA_HOST_MAIN -I $RB -I tests/host/stub -I rpg_monocular_pose_estimator_amd/csrc tests/host/rig_ba_host.cpp \
+    -o $RB/rig_ba_host && $RB/rig_ba_host || rc=1
+rm -rf "$RB"
 exit $rc
