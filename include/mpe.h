@@ -794,6 +794,68 @@ int mpe_rig_fuse_trackers(mpe_tracker* const* trackers, int n, const double* T_c
 int mpe_rig_seed_trackers(mpe_tracker* const* trackers, int n, const double* T_cam_rig, const int* seed,
                           const double rig_pose[16], double time, const double* rig_prev_pose, double prev_time);
 
+/* ---- tracking a body with the whole rig: a camera that sees fewer than four LEDs counts ----
+ * mpe_rig_fuse_trackers takes rows only from cameras whose own tracker solved the frame (>= 4 LEDs in that camera).  The
+ * step below needs no camera to stand on its own: from a predicted rig pose T_pred (rig <- marker frame) it matches every
+ * camera's detections to the projected markers and refines ONE pose over all rows.  A problem = one time step of one
+ * rig; round r = 0, 1, .. starts from T_r (T_0 = T_pred):
+ *  1. project: q = E_c T_r p_m, (u, v) as mpe_rig_optimise_pose_batch computes them; visible when q_z > 0 and u, v finite;
+ *  2. match: the nearest detection of camera c (findCorrespondences' arithmetic: du*du + dv*dv, strict <, first minimum
+ *     wins), kept when sqrt(best) <= tol_c — match_tolerance[c] in round 0, accept_tolerance[c] in later rounds;
+ *  3. one marker per detection: of several markers of a camera on one detection the smallest squared distance keeps it,
+ *     a tie goes to the lowest marker index; the others get no row this round (no second-nearest search);
+ *  4. rows in ascending (camera, marker) order; fewer than min_rows: no pose, reason 1; fewer than min_markers distinct
+ *     markers among them: no pose, reason 2;
+ *  5. r > 0 and the row set equals the previous round's: stop, the result is the previous round's refinement;
+ *  6. refine: mpe_rig_optimise_pose_batch's iteration from T_r over the rows -> T_{r+1}; a non-finite pose: no pose,
+ *     reason 3; stop when r + 1 == max_rounds.
+ * Accept: at the final pose every final row's residual length must be <= accept_tolerance[c], else no pose, reason 4.
+ * This rule is the project's own: the reference validates correspondences with a P3P triple inside ONE camera
+ * (checkCorrespondences), which a camera with two or three rows cannot supply.  It is no initialiser: it needs T_pred.
+ * A record without a pose (status MPE_FRAME_NO_POSE) has T = T_pred and cov = 0; info and match_out still say what was
+ * computed (the last row set built).  With a pose: T, cov (left twist in the rig frame) and gn_iterations are those of
+ * the last refinement, n_corr = rows, n_det = cameras with a row.  info: rounds = refinements run, rows /
+ * distinct_markers of the last row set, reason 0 .. 4, max_residual / rms (pixels) of the accept test (0 when it was not
+ * reached). */
+typedef struct mpe_rig_track_options {
+  int max_rounds;  /* 2; 1 .. 4 */
+  int min_rows;    /* 4; >= 3 */
+  int min_markers; /* 3; >= 1 */
+} mpe_rig_track_options;
+void mpe_rig_track_default_options(mpe_rig_track_options* o);
+typedef struct mpe_rig_track_info {
+  int rounds, rows, distinct_markers, reason;
+  double max_residual, rms;
+} mpe_rig_track_info;
+/* n_problems problems over ONE rig and ONE marker set (markers_xyz n_markers x 3).  The detections (undistorted
+ * pixels) of camera c in problem i are the points [det_begin[i * n_cameras + c], det_begin[i * n_cameras + c + 1]) of
+ * det_xy (x 2), at most MPE_MAX_DETECTIONS of them; det_begin has n_problems * n_cameras + 1 entries.  match_tolerance /
+ * accept_tolerance: n_cameras each, > 0 (+inf allowed).  T_pred: n x 16.  options == NULL: the defaults.  out: n HOST
+ * records; match_out (optional): n_problems * n_cameras * n_markers words, the 1-based detection within that camera's
+ * list that gave (camera, marker) its row, 0 = none; info_out (optional): n records.  One input copy, one launch (a
+ * wave per problem; a problem's record does not depend on the rest of the batch) and one copy back on the handle's
+ * stream.  MPE_ERR_ARG before any device work: a null pointer, n_cameras or n_markers outside 1 .. 16, a negative or
+ * decreasing det_begin, an option out of range, a tolerance that is not > 0, a submission of the handle that is not
+ * collected yet; MPE_ERR_UNSUPPORTED: a camera list of more than MPE_MAX_DETECTIONS detections; nothing is written then.
+ * n_problems == 0: MPE_OK, nothing submitted. */
+int mpe_rig_track_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const double* markers_xyz,
+                        int n_markers, const int* det_begin, const double* det_xy, const double* match_tolerance,
+                        const double* accept_tolerance, int n_problems, const double* T_pred,
+                        const mpe_rig_track_options* options, mpe_result* out, uint32_t* match_out,
+                        mpe_rig_track_info* info_out);
+
+/* After a lock-step call over the n trackers of a rig: ONE problem through mpe_rig_track_batch from rig_pred_pose (rig <-
+ * marker frame at this frame's time).  Tracker i brings its K, the shared marker set and ALL its image points of that
+ * frame (mpe_tracker_get_image_points), whether or not the frame gave that camera a pose; its
+ * nearest_neighbour_pixel_tolerance is the match tolerance and its back_projection_pixel_tolerance the accept tolerance.
+ * (The image points of a camera whose ROI held fewer than four LEDs are those of its whole-image retry; when the retry
+ * found nothing, those of the ROI.)  rig_out: the record; match_out (optional) n x n_markers words; info_out (optional).
+ * Tracker state is not touched.  Returns 1 pose, 0 none, and refuses what mpe_rig_fuse_trackers refuses (MPE_ERR_ARG
+ * before any device work); a tracker with more than MPE_MAX_DETECTIONS image points: MPE_ERR_UNSUPPORTED. */
+int mpe_rig_track_trackers(mpe_tracker* const* trackers, int n, const double* T_cam_rig, const double rig_pred_pose[16],
+                           const mpe_rig_track_options* options, mpe_result* rig_out, uint32_t* match_out,
+                           mpe_rig_track_info* info_out);
+
 /* ---- calibrating the extrinsics of a rig from the body it tracks (a bundle adjustment on the device) ----
  * A recorded sequence of ONE body in front of the rig: view f (a time step) holds the rows [view_begin[f],
  * view_begin[f+1]) of row_camera / row_marker_xyz (x 3) / row_uv (x 2, undistorted pixels), in any camera order, at most

@@ -59,6 +59,20 @@ class MpeRigCamera(C.Structure):  # mpe_rig_camera
     _fields_ = [("K", C.c_double * 9), ("T_cam_rig", C.c_double * 16)]
 
 
+class MpeRigTrackOptions(C.Structure):  # mpe_rig_track_options
+    _fields_ = [("max_rounds", C.c_int), ("min_rows", C.c_int), ("min_markers", C.c_int)]
+
+
+class MpeRigTrackInfo(C.Structure):  # mpe_rig_track_info
+    _fields_ = [("rounds", C.c_int), ("rows", C.c_int), ("distinct_markers", C.c_int), ("reason", C.c_int),
+                ("max_residual", C.c_double), ("rms", C.c_double)]
+
+
+RIG_TRACK_INFO_DTYPE = np.dtype([("rounds", "i4"), ("rows", "i4"), ("distinct_markers", "i4"), ("reason", "i4"),
+                                 ("max_residual", "f8"), ("rms", "f8")])
+assert RIG_TRACK_INFO_DTYPE.itemsize == C.sizeof(MpeRigTrackInfo)
+
+
 class MpeRigCalibrationOptions(C.Structure):  # mpe_rig_calibration_options
     _fields_ = [("reference_camera", C.c_int), ("max_iterations", C.c_int), ("step_tolerance", C.c_double)]
 
@@ -125,7 +139,7 @@ def source_fingerprint():
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
                                   "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
-                                  "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
+                                  "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig_track.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
                                   "mpe_rig_ba_plan.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
@@ -272,6 +286,13 @@ def load_library():
     lib.mpe_rig_optimise_pose_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, dp, dp, C.c_int, dp, C.c_void_p]
     lib.mpe_rig_fuse_trackers.argtypes = [hp, C.c_int, dp, ip, C.c_void_p, ip]
     lib.mpe_rig_seed_trackers.argtypes = [hp, C.c_int, dp, ip, dp, C.c_double, dp, C.c_double]
+    # a body tracked with the whole rig (cameras that see fewer than four LEDs count)
+    lib.mpe_rig_track_default_options.argtypes = [C.POINTER(MpeRigTrackOptions)]
+    lib.mpe_rig_track_default_options.restype = None
+    lib.mpe_rig_track_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, C.c_int, ip, dp, dp, dp, C.c_int, dp,
+                                        C.POINTER(MpeRigTrackOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mpe_rig_track_trackers.argtypes = [hp, C.c_int, dp, dp, C.POINTER(MpeRigTrackOptions), C.c_void_p, C.c_void_p,
+                                           C.c_void_p]
     # the extrinsics of a rig calibrated from the body it tracks
     lib.mpe_rig_calibration_default_options.argtypes = [C.POINTER(MpeRigCalibrationOptions)]
     lib.mpe_rig_calibration_default_options.restype = None
@@ -1011,6 +1032,34 @@ class Handle:
         self._check(rc, "mpe_rig_optimise_pose_batch")
         return rec
 
+    def rig_track_batch(self, cameras, markers, detections, T_pred, match_tol, accept_tol, **options):
+        """mpe_rig_track_batch: the partial-view tracking step of a rig, a batch of problems over ONE rig and ONE marker
+        set in one launch.  cameras: a list of (K 3x3, T_cam_rig 4x4); markers (n_mk, 3); detections: per problem a
+        list of n_cam arrays (k, 2) of undistorted pixels (k = 0 .. 64); T_pred (n, 4, 4), rig <- marker frame;
+        match_tol / accept_tol: a scalar or n_cam values; options: max_rounds, min_rows, min_markers.
+        -> (records [RESULT_DTYPE] (n), match (n, n_cam, n_mk) uint32 — the 1-based detection of (camera, marker)'s row,
+        0 none —, info [RIG_TRACK_INFO_DTYPE] (n))."""
+        n_cam, n = len(cameras), len(detections)
+        cams = pack_rig_cameras(cameras)
+        mk = _f64(markers).reshape(-1, 3)
+        lists = [_f64(d).reshape(-1, 2) for dets in detections for d in dets]
+        assert len(lists) == n * n_cam
+        begin = np.zeros(n * n_cam + 1, np.int32)
+        begin[1:] = np.cumsum([len(d) for d in lists])
+        xy = _f64(np.concatenate(lists) if lists else np.zeros((0, 2))).reshape(-1, 2)
+        T0 = _f64(T_pred).reshape(-1, 16)
+        assert len(T0) == n
+        tm = _f64(np.broadcast_to(_f64(match_tol), (n_cam,)))
+        ta = _f64(np.broadcast_to(_f64(accept_tol), (n_cam,)))
+        rec = np.zeros(n, RESULT_DTYPE)
+        match = np.zeros((n, n_cam, len(mk)), np.uint32)
+        info = np.zeros(n, RIG_TRACK_INFO_DTYPE)
+        rc = self._lib.mpe_rig_track_batch(self._h, cams, n_cam, _dp(mk), len(mk), begin.ctypes.data_as(C.POINTER(C.c_int)),
+                                           _dp(xy), _dp(tm), _dp(ta), n, _dp(T0), rig_track_options(self._lib, options),
+                                           rec.ctypes.data, match.ctypes.data, info.ctypes.data)
+        self._check(rc, "mpe_rig_track_batch")
+        return rec, match, info
+
     def rig_calibrate(self, cameras, views, T_views, reference_camera=0, max_iterations=50, step_tolerance=1e-10):
         """mpe_rig_calibrate: the extrinsics of a rig from a recorded sequence of ONE body (a bundle adjustment on the
         device over the extrinsics of all cameras but reference_camera and one pose per view).  cameras: a list of
@@ -1420,6 +1469,7 @@ class Rig:
         self.T_cam_rig = _f64(T_cam_rig).reshape(len(self.trackers), 16)
         self._ts = (C.c_void_p * len(self.trackers))(*[t._t for t in self.trackers])
         self._prev = None  # (rig pose, time) of the previous step when it fused
+        self._prev2 = None  # the same of the step before that, when both fused (step(partial=True) predicts from the two)
 
     def fuse(self, updated=None):
         """mpe_rig_fuse_trackers over the trackers' last frames -> (fused, record [RESULT_DTYPE] (1), rows per camera)."""
@@ -1434,6 +1484,30 @@ class Rig:
             raise MpeError("mpe_rig_fuse_trackers failed (%d): %s" % (rc, lib.mpe_last_error(self.handle._h).decode()))
         return bool(rc), rec, rows
 
+    def track(self, T_pred, **options):
+        """mpe_rig_track_trackers over the trackers' last frames from the predicted rig pose T_pred (4x4, rig <- marker
+        frame): every camera's image points count, whether or not its own tracker solved the frame.  options:
+        max_rounds, min_rows, min_markers.  -> (pose found, record [RESULT_DTYPE] (1), match (n, n_markers) uint32,
+        info [RIG_TRACK_INFO_DTYPE] (1))."""
+        lib, n = self.handle._lib, len(self.trackers)
+        rec = np.zeros(1, RESULT_DTYPE)
+        match = np.zeros((n, len(self.trackers[0].markers)), np.uint32)
+        info = np.zeros(1, RIG_TRACK_INFO_DTYPE)
+        rc = lib.mpe_rig_track_trackers(self._ts, n, _dp(self.T_cam_rig), _dp(_f64(T_pred).reshape(16)),
+                                        rig_track_options(lib, options), rec.ctypes.data, match.ctypes.data, info.ctypes.data)
+        if rc < 0:
+            raise MpeError("mpe_rig_track_trackers failed (%d): %s" % (rc, lib.mpe_last_error(self.handle._h).decode()))
+        return bool(rc), rec, match, info
+
+    def predict(self, time):
+        """The rig pose the constant-velocity model (predict_pose) gives at `time` from the last two fused steps, the last
+        pose itself when only one step fused, None without a previous rig pose."""
+        if self._prev is None:
+            return None
+        if self._prev2 is None or not self._prev[1] > self._prev2[1]:
+            return self._prev[0].reshape(4, 4).copy()
+        return predict_pose(self._prev[0].reshape(4, 4), self._prev2[0].reshape(4, 4), self._prev[1], self._prev2[1], time)
+
     def seed(self, seed, rig_pose, time, rig_prev_pose=None, prev_time=0.0):
         """mpe_rig_seed_trackers: the trackers with seed[i] != 0 get their pose from the rig's (host state only)."""
         lib, n = self.handle._lib, len(self.trackers)
@@ -1444,24 +1518,54 @@ class Rig:
         if rc < 0:
             raise MpeError("mpe_rig_seed_trackers failed (%d)" % rc)
 
-    def step(self, imgs, times, formats=None, reseed=False):
+    def step(self, imgs, times, formats=None, reseed=False, partial=False):
         """One time step: imgs[i] / times[i] camera i's frame and stamp.  Cameras of one image shape go through
         tracker_estimate_batch_mixed, others (or formats given: as tracker_estimate_batch_formats takes them) through
         tracker_estimate_batch_formats; then the fusion.  reseed: the trackers that did NOT update get the rig's pose
         (and the previous step's, when that step fused), so that their next frame tracks instead of running the brute
-        force.  -> (records (N), info (N, 8), updated (N) — the lock-step entry's, unchanged —, rig record (1), fused)."""
+        force.  partial: with a rig pose from the previous step, predict it to this step's time (predict()) and track
+        the body over ALL cameras' image points (track(): a camera that sees two or three LEDs counts) instead of fusing
+        the cameras that solved the frame on their own; without a previous rig pose, or when tracking finds no pose, the
+        fusion as ever.  self.last_track = (record, match, info) of the step's track() or None.
+        -> (records (N), info (N, 8), updated (N) — the lock-step entry's, unchanged —, rig record (1), fused)."""
         same = formats is None and not _is_torch(imgs[0]) and len({(np.shape(im), np.asarray(im).strides[0]) for im in imgs}) == 1
         if same:
             rec, info, upd = tracker_estimate_batch_mixed(self.trackers, imgs, times)
         else:
             rec, info, upd = tracker_estimate_batch_formats(self.trackers, imgs, times, formats)
-        fused, rig, _ = self.fuse(upd)
         t = float(np.max(_f64(times)))
+        fused, self.last_track = False, None
+        if partial and self._prev is not None:
+            fused, rig, match, tinfo = self.track(self.predict(t))
+            self.last_track = (rig, match, tinfo)
+        if not fused:
+            fused, rig, _ = self.fuse(upd)
         if reseed and fused and not upd.all():
             prev = self._prev
             self.seed(~upd, rig["T"][0], t, None if prev is None else prev[0], 0.0 if prev is None else prev[1])
+        self._prev2 = self._prev if fused else None
         self._prev = (rig["T"][0].copy(), t) if fused else None
         return rec, info, upd, rig, fused
+
+
+def pack_rig_cameras(cameras):
+    """[(K 3x3, T_cam_rig 4x4)] -> mpe_rig_camera array"""
+    cams = (MpeRigCamera * max(1, len(cameras)))()
+    for c, (K, E) in zip(cams, cameras):
+        c.K[:] = _f64(K).reshape(9)
+        c.T_cam_rig[:] = _f64(E).reshape(16)
+    return cams
+
+
+def rig_track_options(lib, options):
+    """max_rounds / min_rows / min_markers over the library's defaults -> MpeRigTrackOptions"""
+    opt = MpeRigTrackOptions()
+    lib.mpe_rig_track_default_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("max_rounds", "min_rows", "min_markers"):
+            raise TypeError("unknown option %r" % k)
+        setattr(opt, k, int(v))
+    return opt
 
 
 def pack_rig_views(cameras, views):

@@ -131,6 +131,10 @@ struct mpe_handle {
   int rig_ba_profile = 0;
   double rig_ba_ms[6] = {0, 0, 0, 0, 0, 0};
   int rig_ba_launches = 0;
+  // option "rig_launch_profile" = 1: mpe_rig_optimise_pose_batch and mpe_rig_track_batch bracket their ONE launch with a
+  // pair of events and leave its device time here (get "rig_launch_ns"); the copies are outside the pair
+  int rig_launch_profile = 0;
+  double rig_launch_ms = 0;
   int pending_track_n = 0;            // a batch submission without its _collect yet: streams in flight
   uint8_t* pending_track_rec = nullptr;
   // How many detections the frames of a pipelined call are expected to carry: picks the voting-kernel variant (from 9

@@ -207,6 +207,14 @@ hipError_t launch_k_nn_wide(const mpe_detections_wide* dets, const double* pred,
 hipError_t launch_k_rig_refine(const mpe_rig_camera* cams, int n_cam, const int* row_begin, const int* row_cam,
                                const double* row_xyz, const double* row_uv, const double* T_init, int n_problems,
                                mpe_result* out, hipStream_t s);
+// k_rig_track, one wave per problem: the partial-view tracking step of a rig (mpe_rig_track.h).  Problem i owns the
+// detection lists det_begin[i * n_cam .. (i + 1) * n_cam] (each at most MPE_MAX_DETECTIONS points: the caller checks),
+// starts from T_pred + 16 i and fills out[i], match[i * n_cam * n_markers ..] and info[i]; everything in device memory.
+hipError_t launch_k_rig_track(const mpe_rig_camera* cams, int n_cam, const double* markers, int n_markers,
+                              const int* det_begin, const double* det_xy, const double* tol_match,
+                              const double* tol_accept, const double* T_pred, int max_rounds, int min_rows,
+                              int min_markers, int n_problems, mpe_result* out, uint32_t* match,
+                              mpe_rig_track_info* info, hipStream_t s);
 // the steps of mpe_rig_calibrate (mpe_rig_ba.h), each a launch of its own: linearise / update over the used views
 // [first, first + count) of one chunk, reduce over the same with flag = 1 when the sums start anew, finish with flag = 1
 // when the cameras take their step; solve and covariance take neither.  The table holds device pointers.

@@ -272,6 +272,7 @@ __device__ __forceinline__ int k3_gauss_newton(int n_c, Row row, double fx, doub
 #define K3_FRAMES_PER_BLOCK 4       // one wave = 4 frames
 #define K3B_THREADS 64              // refinement kernel: one lane per frame
 #include "mpe_rig_gn.h"            // (k_rig_refine's logic, shared with the CPU tier: behind the tail helpers it builds on)
+#include "mpe_rig_track.h"         // (k_rig_track's logic, the same way: behind mpe_rig_gn.h)
 
 // What the validation kernel hands to the refinement kernel, one record per frame (global memory).
 struct TailMid {
@@ -1343,6 +1344,41 @@ hipError_t launch_k_rig_refine(const mpe_rig_camera* cams, int n_cam, const int*
   if (n_problems <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_rig_refine, dim3((unsigned)n_problems), dim3(MPE_RIG_LANES), 0, s, cams, n_cam, row_begin, row_cam,
                      row_xyz, row_uv, T_init, n_problems, out);
+  return hipGetLastError();
+}
+
+// A body tracked with the whole rig (mpe_rig_track_batch): projection, matching, uniqueness, the joint refinement and
+// the acceptance test of mpe_rig_track.h, ONE WAVE PER PROBLEM and one block per problem as k_rig_refine.  A block reads
+// only its own problem's detection lists and predicted pose, the rig's cameras, the markers and the tolerances; the
+// record does not depend on the block's place in the launch.  The host has checked the counts; the options are clamped
+// all the same, and a list is read up to MPE_MAX_DETECTIONS points at the most.
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_track(const mpe_rig_camera* __restrict__ cams, int n_cam,
+                                                             const double* __restrict__ markers, int n_markers,
+                                                             const int* __restrict__ det_begin,
+                                                             const double* __restrict__ det_xy,
+                                                             const double* __restrict__ tol_match,
+                                                             const double* __restrict__ tol_accept,
+                                                             const double* __restrict__ T_pred, int max_rounds,
+                                                             int min_rows, int min_markers, int n_problems,
+                                                             mpe_result* __restrict__ out, uint32_t* __restrict__ match,
+                                                             mpe_rig_track_info* __restrict__ info) {
+  __shared__ RigTrackLds s_track;
+  const int i = blockIdx.x;
+  if (i >= n_problems) return;  // (block-uniform)
+  if (n_cam < 1 || n_cam > MPE_RIG_MAX_CAMERAS || n_markers < 1 || n_markers > MPE_MAX_MARKERS) return;
+  rig_track(s_track, cams, n_cam, markers, n_markers, det_begin + (size_t)i * n_cam, det_xy, tol_match, tol_accept,
+            T_pred + 16 * (size_t)i, min(max(max_rounds, 1), 4), max(min_rows, 3), min_markers, out + i,
+            match + (size_t)i * n_cam * n_markers, info + i);
+}
+hipError_t launch_k_rig_track(const mpe_rig_camera* cams, int n_cam, const double* markers, int n_markers,
+                              const int* det_begin, const double* det_xy, const double* tol_match,
+                              const double* tol_accept, const double* T_pred, int max_rounds, int min_rows,
+                              int min_markers, int n_problems, mpe_result* out, uint32_t* match,
+                              mpe_rig_track_info* info, hipStream_t s) {
+  if (n_problems <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rig_track, dim3((unsigned)n_problems), dim3(MPE_RIG_LANES), 0, s, cams, n_cam, markers, n_markers,
+                     det_begin, det_xy, tol_match, tol_accept, T_pred, max_rounds, min_rows, min_markers, n_problems, out,
+                     match, info);
   return hipGetLastError();
 }
 

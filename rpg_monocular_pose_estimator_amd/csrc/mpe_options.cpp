@@ -292,6 +292,8 @@ int mpe_get_option(mpe_handle* h, const char* name, int* value) {
   else if (n == "rig_ba_record_kb") *value = h->rig_ba_record_kb;
   else if (n == "rig_ba_profile") *value = h->rig_ba_profile;
   else if (n == "rig_ba_launches") *value = h->rig_ba_launches;
+  else if (n == "rig_launch_profile") *value = h->rig_launch_profile;
+  else if (n == "rig_launch_ns") *value = (int)(h->rig_launch_ms * 1e6 + 0.5);
   else if (n.rfind("rig_ba_us_", 0) == 0) {
     static const char* const steps[6] = {"linearise", "reduce", "solve", "update", "finish", "covariance"};
     int k = 0;
@@ -485,6 +487,10 @@ int mpe_set_option(mpe_handle* h, const char* name, int value) {
   }
   if (!std::strcmp(name, "rig_ba_profile")) {  // mpe_rig_calibrate times its launches per step (get "rig_ba_us_*")
     h->rig_ba_profile = value ? 1 : 0;
+    return MPE_OK;
+  }
+  if (!std::strcmp(name, "rig_launch_profile")) {  // the rig's batch entries time their launch (get "rig_launch_ns")
+    h->rig_launch_profile = value ? 1 : 0;
     return MPE_OK;
   }
   if (!std::strcmp(name, "rig_ba_record_kb")) {  // KiB the view records of mpe_rig_calibrate take at a time (0 = 65536)

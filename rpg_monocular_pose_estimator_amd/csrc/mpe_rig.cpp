@@ -1,7 +1,8 @@
 // mpe_rig.cpp — host side of libmpe_hip.so, part 6 (see mpe_host.h): the cameras of a calibrated rig fused into one body
 // pose.  mpe_rig_optimise_pose_batch — the joint Gauss-Newton (k_rig_refine, mpe_k3.hip; logic in mpe_rig_gn.h) over
-// rows that bring their own camera: one input copy, one launch, one copy back.  What works on the trackers of a rig
-// (mpe_rig_fuse_trackers, mpe_rig_seed_trackers) is in mpe_tracker.cpp, beside the state it reads and sets, and comes
+// rows that bring their own camera: one input copy, one launch, one copy back.  mpe_rig_track_batch — the partial-view
+// tracking step (k_rig_track; logic in mpe_rig_track.h), submitted the same way.  What works on the trackers of a rig
+// (mpe_rig_fuse_trackers, mpe_rig_track_trackers, mpe_rig_seed_trackers) is in mpe_tracker.cpp, beside the state it reads and sets, and comes
 // here through the public entry.  mpe_rig_calibrate — the extrinsics of a rig from a recorded sequence of the body: which
 // rows take part and the iteration are mpe_rig_ba_plan.h (shared with the CPU tier), the steps are the k_rig_ba_* kernels
 // (mpe_k3.hip; logic in mpe_rig_ba.h), one launch each on the handle's stream; the host reads two doubles per iteration.
@@ -62,6 +63,30 @@ struct RigBaLaunches {
     out2[0] = host_out[0];
     out2[1] = host_out[1];
     return 0;
+  }
+};
+
+// option "rig_launch_profile": a pair of events around the ONE launch of a batch entry.  begin() in front of the launch,
+// end() behind it (both enqueue only), read() behind the call's synchronisation; the events are given back in any case.
+struct RigLaunchTimer {
+  mpe_handle* h;
+  hipEvent_t a = nullptr, b = nullptr;
+  explicit RigLaunchTimer(mpe_handle* h_) : h(h_) {}
+  hipError_t begin() {
+    if (!h->rig_launch_profile) return hipSuccess;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) e = hipEventRecord(a, h->stream);
+    return e;
+  }
+  hipError_t end() { return (a && b) ? hipEventRecord(b, h->stream) : hipSuccess; }
+  void read() {
+    float ms = 0;
+    if (a && b && hipEventElapsedTime(&ms, a, b) == hipSuccess) h->rig_launch_ms = ms;
+  }
+  ~RigLaunchTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
   }
 };
 
@@ -148,13 +173,110 @@ int mpe_rig_optimise_pose_batch(mpe_handle* h, const mpe_rig_camera* cameras, in
   uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
   mpe_result* d_res = static_cast<mpe_result*>(h->results.p);
   HIP_TRY(h, hipMemcpyAsync(d_in, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
+  RigLaunchTimer timer(h);
+  HIP_TRY(h, timer.begin());
   HIP_TRY(h, launch_k_rig_refine(reinterpret_cast<const mpe_rig_camera*>(d_in), n_cameras,
                                  reinterpret_cast<const int*>(d_in + beg_off), reinterpret_cast<const int*>(d_in + rc_off),
                                  reinterpret_cast<const double*>(d_in + xyz_off), reinterpret_cast<const double*>(d_in + uv_off),
                                  reinterpret_cast<const double*>(d_in + t_off), n_problems, d_res, h->stream));
+  HIP_TRY(h, timer.end());
   HIP_TRY(h, hipMemcpyAsync(mb + back_off, d_res, back_bytes, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  timer.read();
   std::memcpy(out, mb + back_off, back_bytes);
+  return MPE_OK;
+}
+
+void mpe_rig_track_default_options(mpe_rig_track_options* o) {
+  if (!o) return;
+  o->max_rounds = 2;
+  o->min_rows = 4;
+  o->min_markers = 3;
+}
+
+int mpe_rig_track_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const double* markers_xyz,
+                        int n_markers, const int* det_begin, const double* det_xy, const double* match_tolerance,
+                        const double* accept_tolerance, int n_problems, const double* T_pred,
+                        const mpe_rig_track_options* options, mpe_result* out, uint32_t* match_out,
+                        mpe_rig_track_info* info_out) {
+  if (!h || n_problems < 0) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (!cameras) return fail(h, MPE_ERR_ARG, "cameras is null");
+  if (!markers_xyz) return fail(h, MPE_ERR_ARG, "markers_xyz is null");
+  if (!det_begin) return fail(h, MPE_ERR_ARG, "det_begin is null");
+  if (!match_tolerance || !accept_tolerance) return fail(h, MPE_ERR_ARG, "a tolerance array is null");
+  if (!T_pred) return fail(h, MPE_ERR_ARG, "T_pred is null");
+  if (!out) return fail(h, MPE_ERR_ARG, "out is null");
+  if (n_cameras < 1 || n_cameras > MPE_RIG_MAX_CAMERAS) return fail(h, MPE_ERR_ARG, "n_cameras outside 1 .. MPE_RIG_MAX_CAMERAS");
+  if (n_markers < 1 || n_markers > MPE_MAX_MARKERS) return fail(h, MPE_ERR_ARG, "n_markers outside 1 .. MPE_MAX_MARKERS");
+  mpe_rig_track_options opt;
+  mpe_rig_track_default_options(&opt);
+  if (options) opt = *options;
+  if (opt.max_rounds < 1 || opt.max_rounds > 4) return fail(h, MPE_ERR_ARG, "max_rounds outside 1 .. 4");
+  if (opt.min_rows < 3) return fail(h, MPE_ERR_ARG, "min_rows must be >= 3");
+  if (opt.min_markers < 1) return fail(h, MPE_ERR_ARG, "min_markers must be >= 1");
+  for (int c = 0; c < n_cameras; ++c)
+    if (!(match_tolerance[c] > 0) || !(accept_tolerance[c] > 0)) return fail(h, MPE_ERR_ARG, "a tolerance is not > 0");
+  if (n_problems == 0) return MPE_OK;
+  const size_t n_lists = (size_t)n_problems * (size_t)n_cameras;
+  if (det_begin[0] < 0) return fail(h, MPE_ERR_ARG, "det_begin is negative");
+  for (size_t i = 0; i < n_lists; ++i)
+    if (det_begin[i + 1] < det_begin[i]) return fail(h, MPE_ERR_ARG, "det_begin decreases");
+  for (size_t i = 0; i < n_lists; ++i)
+    if (det_begin[i + 1] - det_begin[i] > MPE_MAX_DETECTIONS)
+      return fail(h, MPE_ERR_UNSUPPORTED, "more than MPE_MAX_DETECTIONS detections in a camera's list");
+  const int d0 = det_begin[0], n_det = det_begin[n_lists] - d0;
+  if (n_det > 0 && !det_xy) return fail(h, MPE_ERR_ARG, "det_xy is null");
+  if (h->pending_track_n || h->submit_seq != h->collect_seq)
+    return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+  ENTER(h);
+  // in: [cameras | markers | match tolerances | accept tolerances | det_begin (rebased to 0) | detections | predicted
+  // poses]; back: [records | match words | info records]
+  const size_t cam_bytes = (size_t)n_cameras * sizeof(mpe_rig_camera);
+  const size_t mk_off = up256(cam_bytes);
+  const size_t tm_off = mk_off + up256((size_t)n_markers * 3 * sizeof(double));
+  const size_t ta_off = tm_off + up256((size_t)n_cameras * sizeof(double));
+  const size_t beg_off = ta_off + up256((size_t)n_cameras * sizeof(double));
+  const size_t det_off = beg_off + up256((n_lists + 1) * sizeof(int));
+  const size_t t_off = det_off + up256((size_t)n_det * 2 * sizeof(double));
+  const size_t in_bytes = t_off + (size_t)n_problems * 16 * sizeof(double);
+  const size_t rec_bytes = (size_t)n_problems * sizeof(mpe_result);
+  const size_t match_words = n_lists * (size_t)n_markers;
+  const size_t m_off = up256(rec_bytes);
+  const size_t i_off = m_off + up256(match_words * sizeof(uint32_t));
+  const size_t back_bytes = i_off + (size_t)n_problems * sizeof(mpe_rig_track_info);
+  const size_t back_off = up256(in_bytes);
+  { const int rc = grow_mailbox(h, back_off + back_bytes); if (rc != MPE_OK) return rc; }
+  uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
+  std::memcpy(mb, cameras, cam_bytes);
+  std::memcpy(mb + mk_off, markers_xyz, (size_t)n_markers * 3 * sizeof(double));
+  std::memcpy(mb + tm_off, match_tolerance, (size_t)n_cameras * sizeof(double));
+  std::memcpy(mb + ta_off, accept_tolerance, (size_t)n_cameras * sizeof(double));
+  int* hb = reinterpret_cast<int*>(mb + beg_off);
+  for (size_t i = 0; i <= n_lists; ++i) hb[i] = det_begin[i] - d0;
+  if (n_det > 0) std::memcpy(mb + det_off, det_xy + (size_t)2 * d0, (size_t)n_det * 2 * sizeof(double));
+  std::memcpy(mb + t_off, T_pred, (size_t)n_problems * 16 * sizeof(double));
+  HIP_TRY(h, h->frames.reserve(in_bytes));
+  HIP_TRY(h, h->results.reserve(back_bytes));
+  uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
+  uint8_t* d_back = static_cast<uint8_t*>(h->results.p);
+  HIP_TRY(h, hipMemcpyAsync(d_in, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
+  RigLaunchTimer timer(h);
+  HIP_TRY(h, timer.begin());
+  HIP_TRY(h, launch_k_rig_track(reinterpret_cast<const mpe_rig_camera*>(d_in), n_cameras,
+                                reinterpret_cast<const double*>(d_in + mk_off), n_markers,
+                                reinterpret_cast<const int*>(d_in + beg_off), reinterpret_cast<const double*>(d_in + det_off),
+                                reinterpret_cast<const double*>(d_in + tm_off), reinterpret_cast<const double*>(d_in + ta_off),
+                                reinterpret_cast<const double*>(d_in + t_off), opt.max_rounds, opt.min_rows, opt.min_markers,
+                                n_problems, reinterpret_cast<mpe_result*>(d_back),
+                                reinterpret_cast<uint32_t*>(d_back + m_off),
+                                reinterpret_cast<mpe_rig_track_info*>(d_back + i_off), h->stream));
+  HIP_TRY(h, timer.end());
+  HIP_TRY(h, hipMemcpyAsync(mb + back_off, d_back, back_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  timer.read();
+  std::memcpy(out, mb + back_off, rec_bytes);
+  if (match_out) std::memcpy(match_out, mb + back_off + m_off, match_words * sizeof(uint32_t));
+  if (info_out) std::memcpy(info_out, mb + back_off + i_off, (size_t)n_problems * sizeof(mpe_rig_track_info));
   return MPE_OK;
 }
 

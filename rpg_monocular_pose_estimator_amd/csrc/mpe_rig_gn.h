@@ -111,12 +111,13 @@ __device__ __forceinline__ void rig_row(RigGnLds& G, const T34& T, int j) {
 // index of A[r][c], r <= c, in the packed upper triangle (k3g_tri)
 __device__ __forceinline__ int rig_tri(int r, int c) { return r * 6 - (r * (r - 1)) / 2 + (c - r); }
 
-// One problem on one wave.  cams: the rig's n_cam cameras; rows: n_rows of (camera, marker xyz, pixel uv), 0 <= n_rows <=
-// MPE_RIG_MAX_ROWS and every camera index below n_cam (the caller has checked both); T_init: 16 doubles, row-major.
-// Fills res: T, cov, status, gn_iterations, n_corr = n_rows, n_det = cameras with a row.
-__device__ __forceinline__ void rig_gn_refine(RigGnLds& G, const mpe_rig_camera* cams, int n_cam, const int* row_cam,
-                                              const double* row_xyz, const double* row_uv, int n_rows,
-                                              const double* T_init, mpe_result* res) {
+// The three parts of a refinement: rig_gn_stage brings a problem into LDS, rig_gn_iterate runs the Gauss-Newton over
+// the n_rows rows that are in G.P / G.rc from the pose in G.T (the rig's cameras in G.cam) and leaves the pose in G.T
+// and the factors of the last iteration's A in G.L / G.D, rig_gn_finish writes the record.  rig_gn_refine is the three
+// in a row; k_rig_track (mpe_rig_track.h) stages its rows itself and calls the last two.
+__device__ __forceinline__ void rig_gn_stage(RigGnLds& G, const mpe_rig_camera* cams, int n_cam, const int* row_cam,
+                                             const double* row_xyz, const double* row_uv, int n_rows,
+                                             const double* T_init) {
   RIG_EACH_LANE(l) {
     if (l < n_cam) rig_stage_camera(cams[l], G.cam[l]);
     for (int j = l; j < n_rows; j += MPE_RIG_LANES) {
@@ -131,8 +132,11 @@ __device__ __forceinline__ void rig_gn_refine(RigGnLds& G, const mpe_rig_camera*
     if (l < 36) G.L[l / 6][l % 6] = 0.0;
     if (l < 6) G.D[l] = 0.0;
   }
+}
+
+// -> the iterations run (0 when !run)
+__device__ __forceinline__ int rig_gn_iterate(RigGnLds& G, int n_rows, bool run) {
   int iters = 0;
-  const bool run = n_rows >= 3;  // fewer rows leave the 6x6 normal equations singular (mpe_optimise_pose's rule)
   for (int it = 0; run && it < 500; ++it) {
     T34 T;
     for (int r = 0; r < 3; ++r)
@@ -250,6 +254,11 @@ __device__ __forceinline__ void rig_gn_refine(RigGnLds& G, const mpe_rig_camera*
     }
     if (mx <= 1e-13) break;
   }
+  return iters;
+}
+
+// Fills res: T, cov, status, gn_iterations, n_corr = n_rows, n_det = cameras with a row.
+__device__ __forceinline__ void rig_gn_finish(RigGnLds& G, int n_rows, bool run, int iters, mpe_result* res) {
   // the reference's isFinite on the final pose; the cameras that brought a row
   bool finite = true;
   for (int i = 0; i < 12; ++i) finite = finite && (fabs(G.T[i]) <= 1.7976931348623157e308);
@@ -297,4 +306,16 @@ __device__ __forceinline__ void rig_gn_refine(RigGnLds& G, const mpe_rig_camera*
       res->gn_iterations = iters;
     }
   }
+}
+
+// One problem on one wave.  cams: the rig's n_cam cameras; rows: n_rows of (camera, marker xyz, pixel uv), 0 <= n_rows <=
+// MPE_RIG_MAX_ROWS and every camera index below n_cam (the caller has checked both); T_init: 16 doubles, row-major.
+// Fills res: T, cov, status, gn_iterations, n_corr = n_rows, n_det = cameras with a row.
+__device__ __forceinline__ void rig_gn_refine(RigGnLds& G, const mpe_rig_camera* cams, int n_cam, const int* row_cam,
+                                              const double* row_xyz, const double* row_uv, int n_rows,
+                                              const double* T_init, mpe_result* res) {
+  rig_gn_stage(G, cams, n_cam, row_cam, row_xyz, row_uv, n_rows, T_init);
+  const bool run = n_rows >= 3;  // fewer rows leave the 6x6 normal equations singular (mpe_optimise_pose's rule)
+  const int iters = rig_gn_iterate(G, n_rows, run);
+  rig_gn_finish(G, n_rows, run, iters, res);
 }

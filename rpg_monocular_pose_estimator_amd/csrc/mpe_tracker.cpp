@@ -470,15 +470,15 @@ static Mat4 mat4_from(const double* m) {
   return r;
 }
 
-int mpe_rig_fuse_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const int* updated, mpe_result* rig_out,
-                          int* rows_per_camera) {
+// what mpe_rig_fuse_trackers and mpe_rig_track_trackers refuse before any device work (args_ok: their other pointers)
+static int rig_trackers_refused(mpe_tracker* const* ts, int n, bool args_ok) {
   if (!ts || n < 1 || !ts[0]) return MPE_ERR_ARG;
   mpe_handle* h = ts[0]->h;
   if (n > MPE_RIG_MAX_CAMERAS) {
     mpe_host::set_error(h, "n outside 1 .. MPE_RIG_MAX_CAMERAS");
     return MPE_ERR_ARG;
   }
-  if (!T_cam_rig || !rig_out) {
+  if (!args_ok) {
     mpe_host::set_error(h, "bad argument");
     return MPE_ERR_ARG;
   }
@@ -501,6 +501,13 @@ int mpe_rig_fuse_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig
       return MPE_ERR_ARG;
     }
   }
+  return MPE_OK;
+}
+
+int mpe_rig_fuse_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const int* updated, mpe_result* rig_out,
+                          int* rows_per_camera) {
+  if (const int refused = rig_trackers_refused(ts, n, T_cam_rig && rig_out)) return refused;
+  mpe_handle* h = ts[0]->h;
   std::vector<mpe_rig_camera> cams((size_t)n);
   std::vector<int> row_cam;
   std::vector<double> xyz, uv;
@@ -535,6 +542,32 @@ int mpe_rig_fuse_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig
   const int row_begin[2] = {0, (int)row_cam.size()};
   const int rc = mpe_rig_optimise_pose_batch(h, cams.data(), n, row_begin, row_cam.data(), xyz.data(), uv.data(), 1,
                                              &T0.a[0][0], rig_out);
+  if (rc != MPE_OK) return rc;
+  return rig_out->status == MPE_FRAME_POSE ? 1 : 0;
+}
+
+int mpe_rig_track_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const double rig_pred_pose[16],
+                           const mpe_rig_track_options* options, mpe_result* rig_out, uint32_t* match_out,
+                           mpe_rig_track_info* info_out) {
+  if (const int refused = rig_trackers_refused(ts, n, T_cam_rig && rig_pred_pose && rig_out)) return refused;
+  mpe_handle* h = ts[0]->h;
+  // every tracker's image points of the frame, updated or not (BatchCtx::advance: those of the whole-image retry when
+  // the ROI held fewer than four, those of the ROI when the retry found none)
+  std::vector<mpe_rig_camera> cams((size_t)n);
+  std::vector<int> det_begin((size_t)n + 1, 0);
+  std::vector<double> det_xy, tol_match((size_t)n), tol_accept((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const mpe_tracker* t = ts[i];
+    std::memcpy(cams[(size_t)i].K, t->K, sizeof(t->K));
+    std::memcpy(cams[(size_t)i].T_cam_rig, T_cam_rig + 16 * (size_t)i, 16 * sizeof(double));
+    det_xy.insert(det_xy.end(), t->det.begin(), t->det.end());
+    det_begin[(size_t)i + 1] = (int)det_xy.size() / 2;
+    tol_match[(size_t)i] = t->p.nearest_neighbour_pixel_tolerance;
+    tol_accept[(size_t)i] = t->p.back_projection_pixel_tolerance;
+  }
+  const int rc = mpe_rig_track_batch(h, cams.data(), n, ts[0]->markers.data(), n_markers(ts[0]), det_begin.data(),
+                                     det_xy.data(), tol_match.data(), tol_accept.data(), 1, rig_pred_pose, options, rig_out,
+                                     match_out, info_out);
   if (rc != MPE_OK) return rc;
   return rig_out->status == MPE_FRAME_POSE ? 1 : 0;
 }

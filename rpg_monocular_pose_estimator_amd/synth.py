@@ -241,13 +241,14 @@ def make_sequence(config, n, seed, dt=0.02, lin_speed=0.15, ang_speed=0.6, dropo
 
 
 def make_rig_sequence(config, n, seed, cameras, T_cam_rig, dropout=None, dt=0.02, lin_speed=0.15, ang_speed=0.6,
-                      max_tries=20000):
+                      max_tries=20000, visible=None):
     """One body seen by the cameras of a calibrated rig: ONE smooth trajectory in the rig frame (make_sequence's model:
     constant twist + small jitter, frame k at time k*dt), accepted only when EVERY camera keeps all LEDs in view under
     make_sequence's margins (80 px on the first frame, 20 px / 12 px apart / 0.5 m deep afterwards), and one rendered
     sequence per camera.  cameras: a list of (K, D) (5 plumb-bob coefficients) or (K, D, rows, cols) — a camera without
     a size has the config's; T_cam_rig: (N, 4, 4), camera <- rig; dropout: {camera index: frames rendered with only 2
-    LEDs}.  -> dict(frames [N arrays (n, rows_c, cols_c)], T_true (n, 4, 4) rig <- marker frame, T_true_cam (N, n, 4, 4),
+    LEDs}; visible: {camera index: {frame: marker indices rendered}} — the stated LEDs and only those, in that camera's
+    frame (a body that is partly occluded for every camera; it overrides dropout there).  -> dict(frames [N arrays (n, rows_c, cols_c)], T_true (n, 4, 4) rig <- marker frame, T_true_cam (N, n, 4, 4),
     times, cameras [(K, D, rows, cols)], T_cam_rig, markers)."""
     cfg = CONFIGS[config] if isinstance(config, str) else config
     M = np.asarray(cfg["markers"])
@@ -259,6 +260,8 @@ def make_rig_sequence(config, n, seed, cameras, T_cam_rig, dropout=None, dt=0.02
         cams.append((K, D, rows, cols))
     assert len(cams) == len(E) >= 1
     dropout = {} if dropout is None else {int(c): set(int(k) for k in fr) for c, fr in dropout.items()}
+    visible = {} if visible is None else {int(c): {int(k): sorted(int(m) for m in ms) for k, ms in fr.items()}
+                                          for c, fr in visible.items()}
 
     def in_view(T_rig, margin):
         for (K, D, rows, cols), Ec in zip(cams, E):
@@ -301,7 +304,9 @@ def make_rig_sequence(config, n, seed, cameras, T_cam_rig, dropout=None, dt=0.02
         fr = np.empty((n, rows, cols), np.uint8)
         for k in range(n):
             px = distort_px(project(Ec @ Ts[k], M, K), K, D)
-            if k in dropout.get(c, ()):
+            if k in visible.get(c, ()):
+                px = px[visible[c][k]]
+            elif k in dropout.get(c, ()):
                 px = px[:2]
             fr[k] = render_frame(np.random.default_rng([seed, k, 3, c]), px, rows, cols, cfg["spot_sigma"])
         frames.append(fr)
