@@ -856,6 +856,76 @@ int mpe_rig_track_trackers(mpe_tracker* const* trackers, int n, const double* T_
                            const mpe_rig_track_options* options, mpe_result* rig_out, uint32_t* match_out,
                            mpe_rig_track_info* info_out);
 
+/* ---- finding a body with the whole rig: no camera needs four LEDs, one needs three ----
+ * The tracking step above keeps a pose; this step gets one.  It is initialise() (pose_estimator.cpp:544-702: a P3P
+ * hypothesis from every detection triple x marker permutation, scored by reprojection) widened from one camera to the
+ * rig: hypotheses come from every camera with at least three detections, support is counted in ALL cameras.  A problem =
+ * one time step of one rig: the cameras, one marker set, per camera a list of undistorted detections, a vote tolerance
+ * and an accept tolerance.
+ *  Items.  The cameras in ascending order; camera c with n_c >= 3 detections brings every detection triple i < j < k in
+ *   lexicographic order, crossed with every ordered triple of distinct markers in lexicographic order: item = offset of
+ *   the camera + rank of the combination * P(n_markers, 3) + rank of the permutation.  Bearings as calculateImageVectors,
+ *   the P3P of the voting entries (Kneip; Ferrari's quartic in plain double arithmetic) per root 0 .. 3; a solution
+ *   counts when it is finite.  Hypothesis h = 4 * item + root, T_h = E_c^-1 [R^T | -R^T C] (rig <- marker frame), both
+ *   rigid inverses in closed form.
+ *  Score.  Steps 1 - 3 of mpe_rig_track_batch at T_h, in that entry's arithmetic, with the vote tolerance: the row set
+ *   W_h, rows_h = |W_h|, s2_h = the kept squared distances summed in ascending (camera, marker) order.
+ *  Winner.  The least key (rows descending, s2 ascending, h ascending), a total order: the result cannot depend on how
+ *   the hypotheses were spread over the device.
+ *  Runner-up.  runner_rows = the largest rows_h among the hypotheses that CONTRADICT the winner — some (c, m) has a row in
+ *   W_h that is not the winner's row for (c, m) —, 0 when there is none.
+ *  Decision, in this order: no finite hypothesis: reason 6; best_rows < min_rows: reason 1; fewer than min_markers
+ *   distinct markers in the winner's rows: reason 2; best_rows - runner_rows < min_margin: reason 5 (ambiguous); else the
+ *   tracking rounds of mpe_rig_track_batch from T_pred = T_winner with match tolerance = vote tolerance, the accept
+ *   tolerance, max_rounds, min_rows and min_markers: their reasons (1 .. 4) pass through; reason 0: pose, covariance,
+ *   iterations and counts are the tracking step's.
+ * A record without a pose has T = I, cov = 0 and status MPE_FRAME_NO_POSE.
+ * This acceptance rule is this library's own, like the tracking step's: the reference validates a hypothesis inside the
+ * one camera that produced it, with a fourth LED of that camera, and such a camera does not exist here.  The defaults
+ * come from a numpy prototype (5 markers, 0.1 px noise, 2 stray detections per camera, 3 px tolerance): with the LEDs
+ * spread [3, 3, 2] over three cameras the true row set won with 8 rows while contradicting hypotheses reached 5 - 7; with
+ * [3, 2, 1] or [3, 2, 2], or with clutter alone, wrong hypotheses of 4 - 6 rows appeared that the residual test of the
+ * tracking rounds accepted — hence min_rows above the tracking step's 4 and the strict margin.  Both guards turn a true
+ * problem with few rows into "no pose" (INTEGRATION.md gives the shares); a caller with a tighter tolerance may lower
+ * them.  One camera with three blobs is needed: a rig in which every camera sees at most two has no hypothesis. */
+typedef struct mpe_rig_init_options {
+  int max_rounds;  /* 2; 1 .. 4 */
+  int min_rows;    /* 6; >= 3 */
+  int min_markers; /* 4; >= 1 */
+  int min_margin;  /* 1; >= 0, 0 switches the margin test off */
+} mpe_rig_init_options;
+void mpe_rig_init_default_options(mpe_rig_init_options* o);
+typedef struct mpe_rig_init_info {
+  int reason;                   /* 0 pose; 1 .. 4 as mpe_rig_track_info; 5 ambiguous; 6 no finite hypothesis */
+  int camera;                   /* the winner: its camera (-1 without a winner), */
+  int detection[3], marker[3];  /*  detection triple (0-based within the camera's list) and marker triple, */
+  int root;                     /*  and root */
+  int best_rows, runner_rows;
+  int best_markers;             /* distinct markers among the winner's rows */
+  int64_t n_items;              /* purely combinatorial: sum over the cameras of C(n_c, 3) * P(n_markers, 3) */
+  double best_sum2;
+  double T_hyp[16];             /* T_winner (I without a winner) */
+  mpe_rig_track_info track;     /* the tracking rounds' (zero when they did not run) */
+} mpe_rig_init_info;
+/* n_problems problems over ONE rig and ONE marker set, laid out as mpe_rig_track_batch's (det_begin, det_xy, the two
+ * tolerance arrays, out, match_out, info_out).  match_out: the tracking rounds' when they ran, else the winner's row set.
+ * One input copy, four launches on the handle's stream (vote, winner, runner-up, finish) and one copy back; a problem's
+ * record does not depend on the rest of the batch.  Refusals as mpe_rig_track_batch's (min_margin < 0: MPE_ERR_ARG), and
+ * MPE_ERR_UNSUPPORTED before any device work for a problem of more than 2^22 items (admitted: 16 cameras x 12 detections x
+ * 8 markers = 1.18 M items, 3 cameras x 20 detections x 8 markers = 1.15 M, one list of 64 with 5 markers = 2.5 M;
+ * not: one list of 64 with 6 markers = 5.0 M); nothing is written then.  get "rig_init_submits" counts submissions. */
+int mpe_rig_init_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const double* markers_xyz,
+                       int n_markers, const int* det_begin, const double* det_xy, const double* vote_tolerance,
+                       const double* accept_tolerance, int n_problems, const mpe_rig_init_options* options,
+                       mpe_result* out, uint32_t* match_out, mpe_rig_init_info* info_out);
+
+/* After a lock-step call over the n trackers of a rig: ONE problem through mpe_rig_init_batch.  Tracker i brings its K,
+ * the shared marker set and ALL its image points of that frame; its back_projection_pixel_tolerance is both the vote and
+ * the accept tolerance (initialise() votes with that tolerance too).  Tracker state is not touched.  Returns 1 pose, 0
+ * none, and refuses what mpe_rig_fuse_trackers refuses. */
+int mpe_rig_init_trackers(mpe_tracker* const* trackers, int n, const double* T_cam_rig, const mpe_rig_init_options* options,
+                          mpe_result* rig_out, uint32_t* match_out, mpe_rig_init_info* info_out);
+
 /* ---- calibrating the extrinsics of a rig from the body it tracks (a bundle adjustment on the device) ----
  * A recorded sequence of ONE body in front of the rig: view f (a time step) holds the rows [view_begin[f],
  * view_begin[f+1]) of row_camera / row_marker_xyz (x 3) / row_uv (x 2, undistorted pixels), in any camera order, at most

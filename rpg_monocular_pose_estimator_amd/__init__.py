@@ -16,7 +16,8 @@ from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYP
                       tracker_run_sequences_batch_formats, Rig, MpeRigCamera, RIG_MAX_CAMERAS,
                       RigCalibrator, rig_calibration_start,
                       MpeRigCalibrationOptions, MpeRigCalibrationReport,
-                      MpeRigTrackOptions, MpeRigTrackInfo, RIG_TRACK_INFO_DTYPE)
+                      MpeRigTrackOptions, MpeRigTrackInfo, RIG_TRACK_INFO_DTYPE,
+                      MpeRigInitOptions, MpeRigInitInfo, RIG_INIT_INFO_DTYPE)
 from .pose_estimator import PoseEstimator  # noqa: F401
 
 __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE", "DETECTIONS_DTYPE",
@@ -29,4 +30,5 @@ __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE"
            "tracker_run_sequences_batch_device", "ImageFormat", "tracker_estimate_batch_formats",
            "tracker_run_sequences_batch_formats", "Rig", "MpeRigCamera", "RIG_MAX_CAMERAS", "RigCalibrator",
            "rig_calibration_start", "MpeRigCalibrationOptions",
-           "MpeRigCalibrationReport", "MpeRigTrackOptions", "MpeRigTrackInfo", "RIG_TRACK_INFO_DTYPE"]
+           "MpeRigCalibrationReport", "MpeRigTrackOptions", "MpeRigTrackInfo", "RIG_TRACK_INFO_DTYPE",
+           "MpeRigInitOptions", "MpeRigInitInfo", "RIG_INIT_INFO_DTYPE"]

@@ -73,6 +73,23 @@ RIG_TRACK_INFO_DTYPE = np.dtype([("rounds", "i4"), ("rows", "i4"), ("distinct_ma
 assert RIG_TRACK_INFO_DTYPE.itemsize == C.sizeof(MpeRigTrackInfo)
 
 
+class MpeRigInitOptions(C.Structure):  # mpe_rig_init_options
+    _fields_ = [("max_rounds", C.c_int), ("min_rows", C.c_int), ("min_markers", C.c_int), ("min_margin", C.c_int)]
+
+
+class MpeRigInitInfo(C.Structure):  # mpe_rig_init_info
+    _fields_ = [("reason", C.c_int), ("camera", C.c_int), ("detection", C.c_int * 3), ("marker", C.c_int * 3),
+                ("root", C.c_int), ("best_rows", C.c_int), ("runner_rows", C.c_int), ("best_markers", C.c_int),
+                ("n_items", C.c_int64), ("best_sum2", C.c_double), ("T_hyp", C.c_double * 16), ("track", MpeRigTrackInfo)]
+
+
+RIG_INIT_INFO_DTYPE = np.dtype([("reason", "i4"), ("camera", "i4"), ("detection", "i4", (3,)), ("marker", "i4", (3,)),
+                                ("root", "i4"), ("best_rows", "i4"), ("runner_rows", "i4"), ("best_markers", "i4"),
+                                ("n_items", "i8"), ("best_sum2", "f8"), ("T_hyp", "f8", (16,)),
+                                ("track", RIG_TRACK_INFO_DTYPE)])
+assert RIG_INIT_INFO_DTYPE.itemsize == C.sizeof(MpeRigInitInfo) == 224
+
+
 class MpeRigCalibrationOptions(C.Structure):  # mpe_rig_calibration_options
     _fields_ = [("reference_camera", C.c_int), ("max_iterations", C.c_int), ("step_tolerance", C.c_double)]
 
@@ -139,7 +156,7 @@ def source_fingerprint():
     for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
                                   "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
-                                  "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig_track.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
+                                  "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig_track.h", "mpe_rig_init.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
                                   "mpe_rig_ba_plan.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
@@ -291,6 +308,11 @@ def load_library():
     lib.mpe_rig_track_default_options.restype = None
     lib.mpe_rig_track_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, C.c_int, ip, dp, dp, dp, C.c_int, dp,
                                         C.POINTER(MpeRigTrackOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mpe_rig_init_default_options.argtypes = [C.POINTER(MpeRigInitOptions)]
+    lib.mpe_rig_init_default_options.restype = None
+    lib.mpe_rig_init_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, C.c_int, ip, dp, dp, dp, C.c_int,
+                                       C.POINTER(MpeRigInitOptions), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mpe_rig_init_trackers.argtypes = [hp, C.c_int, dp, C.POINTER(MpeRigInitOptions), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mpe_rig_track_trackers.argtypes = [hp, C.c_int, dp, dp, C.POINTER(MpeRigTrackOptions), C.c_void_p, C.c_void_p,
                                            C.c_void_p]
     # the extrinsics of a rig calibrated from the body it tracks
@@ -1060,6 +1082,30 @@ class Handle:
         self._check(rc, "mpe_rig_track_batch")
         return rec, match, info
 
+    def rig_init_batch(self, cameras, markers, detections, vote_tol, accept_tol, **options):
+        """mpe_rig_init_batch: a body found with the whole rig (no predicted pose; one camera must see three blobs), a
+        batch of problems over ONE rig and ONE marker set.  cameras, markers, detections as rig_track_batch takes them;
+        vote_tol / accept_tol: a scalar or n_cam values; options: max_rounds, min_rows, min_markers, min_margin.
+        -> (records [RESULT_DTYPE] (n), match (n, n_cam, n_mk) uint32, info [RIG_INIT_INFO_DTYPE] (n))."""
+        n_cam, n = len(cameras), len(detections)
+        cams = pack_rig_cameras(cameras)
+        mk = _f64(markers).reshape(-1, 3)
+        lists = [_f64(d).reshape(-1, 2) for dets in detections for d in dets]
+        assert len(lists) == n * n_cam
+        begin = np.zeros(n * n_cam + 1, np.int32)
+        begin[1:] = np.cumsum([len(d) for d in lists])
+        xy = _f64(np.concatenate(lists) if lists else np.zeros((0, 2))).reshape(-1, 2)
+        tv = _f64(np.broadcast_to(_f64(vote_tol), (n_cam,)))
+        ta = _f64(np.broadcast_to(_f64(accept_tol), (n_cam,)))
+        rec = np.zeros(n, RESULT_DTYPE)
+        match = np.zeros((n, n_cam, len(mk)), np.uint32)
+        info = np.zeros(n, RIG_INIT_INFO_DTYPE)
+        rc = self._lib.mpe_rig_init_batch(self._h, cams, n_cam, _dp(mk), len(mk), begin.ctypes.data_as(C.POINTER(C.c_int)),
+                                          _dp(xy), _dp(tv), _dp(ta), n, rig_init_options(self._lib, options),
+                                          rec.ctypes.data, match.ctypes.data, info.ctypes.data)
+        self._check(rc, "mpe_rig_init_batch")
+        return rec, match, info
+
     def rig_calibrate(self, cameras, views, T_views, reference_camera=0, max_iterations=50, step_tolerance=1e-10):
         """mpe_rig_calibrate: the extrinsics of a rig from a recorded sequence of ONE body (a bundle adjustment on the
         device over the extrinsics of all cameras but reference_camera and one pose per view).  cameras: a list of
@@ -1470,6 +1516,7 @@ class Rig:
         self._ts = (C.c_void_p * len(self.trackers))(*[t._t for t in self.trackers])
         self._prev = None  # (rig pose, time) of the previous step when it fused
         self._prev2 = None  # the same of the step before that, when both fused (step(partial=True) predicts from the two)
+        self.last_track = self.last_init = None
 
     def fuse(self, updated=None):
         """mpe_rig_fuse_trackers over the trackers' last frames -> (fused, record [RESULT_DTYPE] (1), rows per camera)."""
@@ -1499,6 +1546,21 @@ class Rig:
             raise MpeError("mpe_rig_track_trackers failed (%d): %s" % (rc, lib.mpe_last_error(self.handle._h).decode()))
         return bool(rc), rec, match, info
 
+    def init(self, **options):
+        """mpe_rig_init_trackers over the trackers' last frames: the body found with the whole rig, without a predicted
+        pose (P3P hypotheses from every camera with three image points, support counted in all cameras).  options:
+        max_rounds, min_rows, min_markers, min_margin.  -> (pose found, record [RESULT_DTYPE] (1), match (n, n_markers)
+        uint32, info [RIG_INIT_INFO_DTYPE] (1))."""
+        lib, n = self.handle._lib, len(self.trackers)
+        rec = np.zeros(1, RESULT_DTYPE)
+        match = np.zeros((n, len(self.trackers[0].markers)), np.uint32)
+        info = np.zeros(1, RIG_INIT_INFO_DTYPE)
+        rc = lib.mpe_rig_init_trackers(self._ts, n, _dp(self.T_cam_rig), rig_init_options(lib, options), rec.ctypes.data,
+                                       match.ctypes.data, info.ctypes.data)
+        if rc < 0:
+            raise MpeError("mpe_rig_init_trackers failed (%d): %s" % (rc, lib.mpe_last_error(self.handle._h).decode()))
+        return bool(rc), rec, match, info
+
     def predict(self, time):
         """The rig pose the constant-velocity model (predict_pose) gives at `time` from the last two fused steps, the last
         pose itself when only one step fused, None without a previous rig pose."""
@@ -1518,7 +1580,7 @@ class Rig:
         if rc < 0:
             raise MpeError("mpe_rig_seed_trackers failed (%d)" % rc)
 
-    def step(self, imgs, times, formats=None, reseed=False, partial=False):
+    def step(self, imgs, times, formats=None, reseed=False, partial=False, init=False):
         """One time step: imgs[i] / times[i] camera i's frame and stamp.  Cameras of one image shape go through
         tracker_estimate_batch_mixed, others (or formats given: as tracker_estimate_batch_formats takes them) through
         tracker_estimate_batch_formats; then the fusion.  reseed: the trackers that did NOT update get the rig's pose
@@ -1526,7 +1588,10 @@ class Rig:
         force.  partial: with a rig pose from the previous step, predict it to this step's time (predict()) and track
         the body over ALL cameras' image points (track(): a camera that sees two or three LEDs counts) instead of fusing
         the cameras that solved the frame on their own; without a previous rig pose, or when tracking finds no pose, the
-        fusion as ever.  self.last_track = (record, match, info) of the step's track() or None.
+        fusion as ever.  self.last_track = (record, match, info) of the step's track() or None.  init: a step that ends
+        with no rig pose — after the fusion, and after the tracking where partial is on — runs init(); a pose found there
+        counts as fused (reseed seeds the trackers from it, the next step tracks from it).  self.last_init = (record,
+        match, info) of the step's init() or None.
         -> (records (N), info (N, 8), updated (N) — the lock-step entry's, unchanged —, rig record (1), fused)."""
         same = formats is None and not _is_torch(imgs[0]) and len({(np.shape(im), np.asarray(im).strides[0]) for im in imgs}) == 1
         if same:
@@ -1540,6 +1605,12 @@ class Rig:
             self.last_track = (rig, match, tinfo)
         if not fused:
             fused, rig, _ = self.fuse(upd)
+        self.last_init = None
+        if init and not fused:
+            fused, found, match, iinfo = self.init()
+            self.last_init = (found, match, iinfo)
+            if fused:
+                rig = found
         if reseed and fused and not upd.all():
             prev = self._prev
             self.seed(~upd, rig["T"][0], t, None if prev is None else prev[0], 0.0 if prev is None else prev[1])
@@ -1563,6 +1634,17 @@ def rig_track_options(lib, options):
     lib.mpe_rig_track_default_options(C.byref(opt))
     for k, v in options.items():
         if k not in ("max_rounds", "min_rows", "min_markers"):
+            raise TypeError("unknown option %r" % k)
+        setattr(opt, k, int(v))
+    return opt
+
+
+def rig_init_options(lib, options):
+    """max_rounds / min_rows / min_markers / min_margin over the library's defaults -> MpeRigInitOptions"""
+    opt = MpeRigInitOptions()
+    lib.mpe_rig_init_default_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("max_rounds", "min_rows", "min_markers", "min_margin"):
             raise TypeError("unknown option %r" % k)
         setattr(opt, k, int(v))
     return opt

@@ -117,6 +117,8 @@ struct mpe_handle {
   // get "bruteforce_submits": device submissions of the brute-force solve entries (mpe_solve_bruteforce[_batch],
   // mpe_initialise: one each; mpe_solve_bruteforce_batch_setups: one for a fused call, one per set-up with items otherwise)
   long long bruteforce_submits = 0;
+  // get "rig_init_submits": device submissions of mpe_rig_init_batch (one per call with a problem in it)
+  long long rig_init_submits = 0;
   // the *_wide entries (mpe_wide.cpp): get "wide_frames" — detection sets mpe_solve_bruteforce_batch_wide has solved;
   // option "wide_block_cap" (tests): blocks per set of the wide voting launch at most, 0 = four per compute unit
   long long wide_frames = 0;
@@ -131,7 +133,8 @@ struct mpe_handle {
   int rig_ba_profile = 0;
   double rig_ba_ms[6] = {0, 0, 0, 0, 0, 0};
   int rig_ba_launches = 0;
-  // option "rig_launch_profile" = 1: mpe_rig_optimise_pose_batch and mpe_rig_track_batch bracket their ONE launch with a
+  // option "rig_launch_profile" = 1: mpe_rig_optimise_pose_batch and mpe_rig_track_batch bracket their ONE launch (and
+  // mpe_rig_init_batch its four) with a
   // pair of events and leave its device time here (get "rig_launch_ns"); the copies are outside the pair
   int rig_launch_profile = 0;
   double rig_launch_ms = 0;

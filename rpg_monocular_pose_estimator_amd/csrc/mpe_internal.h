@@ -215,6 +215,26 @@ hipError_t launch_k_rig_track(const mpe_rig_camera* cams, int n_cam, const doubl
                               const double* tol_accept, const double* T_pred, int max_rounds, int min_rows,
                               int min_markers, int n_problems, mpe_result* out, uint32_t* match,
                               mpe_rig_track_info* info, hipStream_t s);
+// The rig initialiser (mpe_rig_init.h): k_rig_init_vote, k_rig_init_winner, k_rig_init_vote again against the winner's
+// row set, k_rig_init_finish, in this order on s.  Problem i owns the detection lists det_begin[i * n_cam ..] and the
+// blocks [chunk_begin[i], chunk_begin[i + 1]) of the vote (one per 128 of its items: the caller has counted them and
+// refused more than 2^22), n_chunks = chunk_begin[n_problems]; keys / runners: n_chunks entries, winner: n_problems,
+// win_rows: 256 bytes per problem; out, match and info as launch_k_rig_track's.  Everything in device memory.
+struct RigInitKey;
+enum { MPE_RIG_INIT_KEY_BYTES = 16, MPE_RIG_INIT_BLOCK_ITEMS = 128, MPE_RIG_INIT_ITEM_CAP = 1 << 22 };  // (mpe_k3.hip asserts them)
+struct RigInitDev {
+  const mpe_rig_camera* cams;
+  const double *markers, *det_xy, *tol_vote, *tol_accept;
+  const int *det_begin, *chunk_begin;
+  int n_cam, n_markers, n_problems, n_chunks, max_rounds, min_rows, min_markers, min_margin;
+  RigInitKey *keys, *winner;
+  int* runners;
+  unsigned char* win_rows;
+  mpe_result* out;
+  uint32_t* match;
+  mpe_rig_init_info* info;
+};
+hipError_t launch_k_rig_init(const RigInitDev& d, hipStream_t s);
 // the steps of mpe_rig_calibrate (mpe_rig_ba.h), each a launch of its own: linearise / update over the used views
 // [first, first + count) of one chunk, reduce over the same with flag = 1 when the sums start anew, finish with flag = 1
 // when the cameras take their step; solve and covariance take neither.  The table holds device pointers.

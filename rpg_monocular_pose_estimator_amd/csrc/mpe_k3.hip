@@ -273,6 +273,7 @@ __device__ __forceinline__ int k3_gauss_newton(int n_c, Row row, double fx, doub
 #define K3B_THREADS 64              // refinement kernel: one lane per frame
 #include "mpe_rig_gn.h"            // (k_rig_refine's logic, shared with the CPU tier: behind the tail helpers it builds on)
 #include "mpe_rig_track.h"         // (k_rig_track's logic, the same way: behind mpe_rig_gn.h)
+#include "mpe_rig_init.h"          // (the rig initialiser's: behind mpe_rig_track.h, whose rounds it ends with)
 
 // What the validation kernel hands to the refinement kernel, one record per frame (global memory).
 struct TailMid {
@@ -1379,6 +1380,147 @@ hipError_t launch_k_rig_track(const mpe_rig_camera* cams, int n_cam, const doubl
   hipLaunchKernelGGL(k_rig_track, dim3((unsigned)n_problems), dim3(MPE_RIG_LANES), 0, s, cams, n_cam, markers, n_markers,
                      det_begin, det_xy, tol_match, tol_accept, T_pred, max_rounds, min_rows, min_markers, n_problems, out,
                      match, info);
+  return hipGetLastError();
+}
+
+// A body found with the whole rig (mpe_rig_init_batch; logic in mpe_rig_init.h).  Four launches on one stream, kernel
+// boundaries order them: k_rig_init_vote (mode 0) — a block per MPE_RIG_INIT_CHUNK items of a problem, one item per lane
+// for the P3P, each lane scores its four roots in all cameras, the block writes ONE best key; k_rig_init_winner — a block
+// per problem takes the keys to the winner in index order and scores it once more for its row set; k_rig_init_vote
+// (mode 1) — the same items against the winner's row set, the block writes the most rows of a contradicting hypothesis;
+// k_rig_init_finish — a wave per problem: the runner-up, the decision, rig_track unchanged.  No atomics, no sum across
+// lanes; the keys are totally ordered, so neither the chunk size nor the block count shows in the result.
+// chunk_begin (n_problems + 1): problem i owns the blocks [chunk_begin[i], chunk_begin[i + 1]).
+__device__ __forceinline__ int rig_init_problem_of(const int* __restrict__ chunk_begin, int n_problems, int block) {
+  int lo = 0, hi = n_problems - 1;  // the last i with chunk_begin[i] <= block
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (chunk_begin[mid] <= block) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(MPE_RIG_INIT_LANES) void k_rig_init_vote(const mpe_rig_camera* __restrict__ cams, int n_cam,
+                                                                      const double* __restrict__ markers, int n_markers,
+                                                                      const int* __restrict__ det_begin,
+                                                                      const double* __restrict__ det_xy,
+                                                                      const double* __restrict__ tol_vote,
+                                                                      const int* __restrict__ chunk_begin, int n_problems,
+                                                                      int mode, const RigInitKey* __restrict__ winner,
+                                                                      const unsigned char* __restrict__ win_rows,
+                                                                      RigInitKey* __restrict__ keys, int* __restrict__ runners) {
+  __shared__ RigInitLds S;
+  static_assert(sizeof(RigInitLds) <= 40 * 1024, "four blocks of k_rig_init_vote on a compute unit");
+  static_assert(sizeof(RigInitLds::d2) >= MPE_RIG_INIT_LANES * (sizeof(RigInitKey) + sizeof(int)), "the block's reduction goes through S.d2");
+  if (n_cam < 1 || n_cam > MPE_RIG_MAX_CAMERAS || n_markers < 1 || n_markers > MPE_MAX_MARKERS) return;
+  const int ln = (int)threadIdx.x, blk = (int)blockIdx.x;
+  const int i = rig_init_problem_of(chunk_begin, n_problems, blk);  // (block-uniform)
+  if (mode == 1 && winner[i].h < 0) {  // no hypothesis, nothing contradicts
+    if (ln == 0) runners[blk] = 0;
+    return;
+  }
+  rig_init_stage(S, ln, MPE_RIG_INIT_LANES, cams, n_cam, markers, n_markers, det_begin + (size_t)i * n_cam, det_xy, tol_vote,
+                 mode == 1 ? win_rows + (size_t)i * MPE_RIG_MAX_ROWS : nullptr);
+  __syncthreads();
+  const int n_items = S.off[n_cam] < MPE_RIG_INIT_MAX_ITEMS ? S.off[n_cam] : MPE_RIG_INIT_MAX_ITEMS;
+  const int first = (blk - chunk_begin[i]) * MPE_RIG_INIT_CHUNK;
+  RigInitKey key = rig_init_no_key();
+  int runner = 0;
+  for (int k = 0; k < MPE_RIG_INIT_ITEMS_PER_LANE; ++k) {
+    const int item = first + k * MPE_RIG_INIT_LANES + ln;
+    if (item < n_items) rig_init_item(S, ln, n_cam, n_markers, item, mode, key, runner);
+  }
+  __syncthreads();  // every lane is done with its columns of S.d2
+  RigInitKey* rk = reinterpret_cast<RigInitKey*>(&S.d2[0][0]);
+  int* rr = reinterpret_cast<int*>(rk + MPE_RIG_INIT_LANES);
+  rk[ln] = key;
+  rr[ln] = runner;
+  __syncthreads();
+  for (int w = MPE_RIG_INIT_LANES / 2; w > 0; w >>= 1) {
+    if (ln < w) {
+      if (rig_init_better(rk[ln + w], rk[ln])) rk[ln] = rk[ln + w];
+      if (rr[ln + w] > rr[ln]) rr[ln] = rr[ln + w];
+    }
+    __syncthreads();
+  }
+  if (ln == 0) {
+    if (mode == 0) keys[blk] = rk[0]; else runners[blk] = rr[0];
+  }
+}
+__global__ __launch_bounds__(MPE_RIG_INIT_LANES) void k_rig_init_winner(const mpe_rig_camera* __restrict__ cams, int n_cam,
+                                                                        const double* __restrict__ markers, int n_markers,
+                                                                        const int* __restrict__ det_begin,
+                                                                        const double* __restrict__ det_xy,
+                                                                        const double* __restrict__ tol_vote,
+                                                                        const int* __restrict__ chunk_begin, int n_problems,
+                                                                        const RigInitKey* __restrict__ keys,
+                                                                        RigInitKey* __restrict__ winner,
+                                                                        unsigned char* __restrict__ win_rows,
+                                                                        mpe_rig_init_info* __restrict__ info) {
+  __shared__ RigInitLds S;
+  const int ln = (int)threadIdx.x, i = (int)blockIdx.x;
+  if (i >= n_problems || n_cam < 1 || n_cam > MPE_RIG_MAX_CAMERAS || n_markers < 1 || n_markers > MPE_MAX_MARKERS) return;
+  RigInitKey key = rig_init_no_key();
+  for (int b = chunk_begin[i] + ln; b < chunk_begin[i + 1]; b += MPE_RIG_INIT_LANES)
+    if (rig_init_better(keys[b], key)) key = keys[b];
+  rig_init_stage(S, ln, MPE_RIG_INIT_LANES, cams, n_cam, markers, n_markers, det_begin + (size_t)i * n_cam, det_xy, tol_vote,
+                 nullptr);
+  RigInitKey* rk = reinterpret_cast<RigInitKey*>(&S.d2[0][0]);
+  rk[ln] = key;
+  __syncthreads();
+  for (int w = MPE_RIG_INIT_LANES / 2; w > 0; w >>= 1) {
+    if (ln < w && rig_init_better(rk[ln + w], rk[ln])) rk[ln] = rk[ln + w];
+    __syncthreads();
+  }
+  key = rk[0];
+  __syncthreads();  // (lane 0 scores through S.d2 next)
+  if (ln == 0) {
+    winner[i] = key;
+    rig_init_winner(S, 0, n_cam, n_markers, key, win_rows + (size_t)i * MPE_RIG_MAX_ROWS, info + i);
+  }
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_rig_init_finish(const mpe_rig_camera* __restrict__ cams, int n_cam,
+                                                                   const double* __restrict__ markers, int n_markers,
+                                                                   const int* __restrict__ det_begin,
+                                                                   const double* __restrict__ det_xy,
+                                                                   const double* __restrict__ tol_vote,
+                                                                   const double* __restrict__ tol_accept,
+                                                                   const int* __restrict__ chunk_begin, int n_problems,
+                                                                   const int* __restrict__ runners,
+                                                                   const unsigned char* __restrict__ win_rows, int max_rounds,
+                                                                   int min_rows, int min_markers, int min_margin,
+                                                                   mpe_result* __restrict__ out, uint32_t* __restrict__ match,
+                                                                   mpe_rig_init_info* info) {
+  __shared__ RigTrackLds s_track;
+  __shared__ int s_runner[MPE_RIG_LANES];
+  const int ln = (int)threadIdx.x, i = (int)blockIdx.x;
+  if (i >= n_problems || n_cam < 1 || n_cam > MPE_RIG_MAX_CAMERAS || n_markers < 1 || n_markers > MPE_MAX_MARKERS) return;
+  int r = 0;
+  for (int b = chunk_begin[i] + ln; b < chunk_begin[i + 1]; b += MPE_RIG_LANES) r = runners[b] > r ? runners[b] : r;
+  s_runner[ln] = r;
+  wave_sync();
+  int runner = 0;
+  for (int k = 0; k < MPE_RIG_LANES; ++k) runner = s_runner[k] > runner ? s_runner[k] : runner;
+  rig_init_finish(s_track, cams, n_cam, markers, n_markers, det_begin + (size_t)i * n_cam, det_xy, tol_vote, tol_accept,
+                  win_rows + (size_t)i * MPE_RIG_MAX_ROWS, runner, min(max(max_rounds, 1), 4), max(min_rows, 3), min_markers,
+                  min_margin, out + i, match + (size_t)i * n_cam * n_markers, info + i);
+}
+hipError_t launch_k_rig_init(const RigInitDev& d, hipStream_t s) {
+  static_assert(sizeof(RigInitKey) == MPE_RIG_INIT_KEY_BYTES && MPE_RIG_INIT_CHUNK == MPE_RIG_INIT_BLOCK_ITEMS &&
+                    MPE_RIG_INIT_MAX_ITEMS == MPE_RIG_INIT_ITEM_CAP,
+                "what the host sizes its buffers and counts its blocks with");
+  if (d.n_problems <= 0) return hipSuccess;
+  const dim3 lanes(MPE_RIG_INIT_LANES), problems((unsigned)d.n_problems);
+  if (d.n_chunks > 0)
+    hipLaunchKernelGGL(k_rig_init_vote, dim3((unsigned)d.n_chunks), lanes, 0, s, d.cams, d.n_cam, d.markers, d.n_markers,
+                       d.det_begin, d.det_xy, d.tol_vote, d.chunk_begin, d.n_problems, 0, nullptr, nullptr, d.keys, d.runners);
+  hipLaunchKernelGGL(k_rig_init_winner, problems, lanes, 0, s, d.cams, d.n_cam, d.markers, d.n_markers, d.det_begin, d.det_xy,
+                     d.tol_vote, d.chunk_begin, d.n_problems, d.keys, d.winner, d.win_rows, d.info);
+  if (d.n_chunks > 0)
+    hipLaunchKernelGGL(k_rig_init_vote, dim3((unsigned)d.n_chunks), lanes, 0, s, d.cams, d.n_cam, d.markers, d.n_markers,
+                       d.det_begin, d.det_xy, d.tol_vote, d.chunk_begin, d.n_problems, 1, d.winner, d.win_rows, d.keys, d.runners);
+  hipLaunchKernelGGL(k_rig_init_finish, problems, dim3(MPE_RIG_LANES), 0, s, d.cams, d.n_cam, d.markers, d.n_markers,
+                     d.det_begin, d.det_xy, d.tol_vote, d.tol_accept, d.chunk_begin, d.n_problems, d.runners, d.win_rows,
+                     d.max_rounds, d.min_rows, d.min_markers, d.min_margin, d.out, d.match, d.info);
   return hipGetLastError();
 }
 

@@ -1,8 +1,10 @@
 // mpe_rig.cpp — host side of libmpe_hip.so, part 6 (see mpe_host.h): the cameras of a calibrated rig fused into one body
 // pose.  mpe_rig_optimise_pose_batch — the joint Gauss-Newton (k_rig_refine, mpe_k3.hip; logic in mpe_rig_gn.h) over
 // rows that bring their own camera: one input copy, one launch, one copy back.  mpe_rig_track_batch — the partial-view
-// tracking step (k_rig_track; logic in mpe_rig_track.h), submitted the same way.  What works on the trackers of a rig
-// (mpe_rig_fuse_trackers, mpe_rig_track_trackers, mpe_rig_seed_trackers) is in mpe_tracker.cpp, beside the state it reads and sets, and comes
+// tracking step (k_rig_track; logic in mpe_rig_track.h), submitted the same way.  mpe_rig_init_batch — the body found
+// with the whole rig (k_rig_init_vote / _winner / _finish; logic in mpe_rig_init.h): the host counts the items and the
+// voting blocks of every problem, one input copy, four launches, one copy back.  What works on the trackers of a rig
+// (mpe_rig_fuse_trackers, mpe_rig_track_trackers, mpe_rig_init_trackers, mpe_rig_seed_trackers) is in mpe_tracker.cpp, beside the state it reads and sets, and comes
 // here through the public entry.  mpe_rig_calibrate — the extrinsics of a rig from a recorded sequence of the body: which
 // rows take part and the iteration are mpe_rig_ba_plan.h (shared with the CPU tier), the steps are the k_rig_ba_* kernels
 // (mpe_k3.hip; logic in mpe_rig_ba.h), one launch each on the handle's stream; the host reads two doubles per iteration.
@@ -277,6 +279,131 @@ int mpe_rig_track_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_came
   std::memcpy(out, mb + back_off, rec_bytes);
   if (match_out) std::memcpy(match_out, mb + back_off + m_off, match_words * sizeof(uint32_t));
   if (info_out) std::memcpy(info_out, mb + back_off + i_off, (size_t)n_problems * sizeof(mpe_rig_track_info));
+  return MPE_OK;
+}
+
+void mpe_rig_init_default_options(mpe_rig_init_options* o) {
+  if (!o) return;
+  o->max_rounds = 2;
+  o->min_rows = 6;
+  o->min_markers = 4;
+  o->min_margin = 1;
+}
+
+int mpe_rig_init_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const double* markers_xyz,
+                       int n_markers, const int* det_begin, const double* det_xy, const double* vote_tolerance,
+                       const double* accept_tolerance, int n_problems, const mpe_rig_init_options* options,
+                       mpe_result* out, uint32_t* match_out, mpe_rig_init_info* info_out) {
+  if (!h || n_problems < 0) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (!cameras) return fail(h, MPE_ERR_ARG, "cameras is null");
+  if (!markers_xyz) return fail(h, MPE_ERR_ARG, "markers_xyz is null");
+  if (!det_begin) return fail(h, MPE_ERR_ARG, "det_begin is null");
+  if (!vote_tolerance || !accept_tolerance) return fail(h, MPE_ERR_ARG, "a tolerance array is null");
+  if (!out) return fail(h, MPE_ERR_ARG, "out is null");
+  if (n_cameras < 1 || n_cameras > MPE_RIG_MAX_CAMERAS) return fail(h, MPE_ERR_ARG, "n_cameras outside 1 .. MPE_RIG_MAX_CAMERAS");
+  if (n_markers < 1 || n_markers > MPE_MAX_MARKERS) return fail(h, MPE_ERR_ARG, "n_markers outside 1 .. MPE_MAX_MARKERS");
+  mpe_rig_init_options opt;
+  mpe_rig_init_default_options(&opt);
+  if (options) opt = *options;
+  if (opt.max_rounds < 1 || opt.max_rounds > 4) return fail(h, MPE_ERR_ARG, "max_rounds outside 1 .. 4");
+  if (opt.min_rows < 3) return fail(h, MPE_ERR_ARG, "min_rows must be >= 3");
+  if (opt.min_markers < 1) return fail(h, MPE_ERR_ARG, "min_markers must be >= 1");
+  if (opt.min_margin < 0) return fail(h, MPE_ERR_ARG, "min_margin must be >= 0");
+  for (int c = 0; c < n_cameras; ++c)
+    if (!(vote_tolerance[c] > 0) || !(accept_tolerance[c] > 0)) return fail(h, MPE_ERR_ARG, "a tolerance is not > 0");
+  if (n_problems == 0) return MPE_OK;
+  const size_t n_lists = (size_t)n_problems * (size_t)n_cameras;
+  if (det_begin[0] < 0) return fail(h, MPE_ERR_ARG, "det_begin is negative");
+  for (size_t i = 0; i < n_lists; ++i)
+    if (det_begin[i + 1] < det_begin[i]) return fail(h, MPE_ERR_ARG, "det_begin decreases");
+  for (size_t i = 0; i < n_lists; ++i)
+    if (det_begin[i + 1] - det_begin[i] > MPE_MAX_DETECTIONS)
+      return fail(h, MPE_ERR_UNSUPPORTED, "more than MPE_MAX_DETECTIONS detections in a camera's list");
+  // the items of every problem, counted from det_begin alone, and the blocks that vote on them
+  const long long perms = n_markers >= 3 ? (long long)n_markers * (n_markers - 1) * (n_markers - 2) : 0;
+  std::vector<int> chunk_begin((size_t)n_problems + 1, 0);
+  for (int i = 0; i < n_problems; ++i) {
+    long long items = 0;
+    for (int c = 0; c < n_cameras; ++c) {
+      const long long n = det_begin[(size_t)i * n_cameras + c + 1] - det_begin[(size_t)i * n_cameras + c];
+      if (n >= 3) items += n * (n - 1) * (n - 2) / 6 * perms;
+    }
+    if (items > MPE_RIG_INIT_ITEM_CAP) return fail(h, MPE_ERR_UNSUPPORTED, "more than 2^22 items (detection triples x marker permutations) in a problem");
+    const long long blocks = (items + MPE_RIG_INIT_BLOCK_ITEMS - 1) / MPE_RIG_INIT_BLOCK_ITEMS;
+    if (chunk_begin[(size_t)i] + blocks > 0x7fffffffLL) return fail(h, MPE_ERR_UNSUPPORTED, "more than 2^31 voting blocks in a call");
+    chunk_begin[(size_t)i + 1] = chunk_begin[(size_t)i] + (int)blocks;
+  }
+  const int n_chunks = chunk_begin[(size_t)n_problems];
+  const int d0 = det_begin[0], n_det = det_begin[n_lists] - d0;
+  if (n_det > 0 && !det_xy) return fail(h, MPE_ERR_ARG, "det_xy is null");
+  if (h->pending_track_n || h->submit_seq != h->collect_seq)
+    return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+  ENTER(h);
+  // in: [cameras | markers | vote tolerances | accept tolerances | det_begin (rebased to 0) | chunk_begin | detections];
+  // back: [records | match words | info records]; on the device only: [keys | winners | runners | winner row sets]
+  const size_t cam_bytes = (size_t)n_cameras * sizeof(mpe_rig_camera);
+  const size_t mk_off = up256(cam_bytes);
+  const size_t tv_off = mk_off + up256((size_t)n_markers * 3 * sizeof(double));
+  const size_t ta_off = tv_off + up256((size_t)n_cameras * sizeof(double));
+  const size_t beg_off = ta_off + up256((size_t)n_cameras * sizeof(double));
+  const size_t chk_off = beg_off + up256((n_lists + 1) * sizeof(int));
+  const size_t det_off = chk_off + up256(((size_t)n_problems + 1) * sizeof(int));
+  const size_t in_bytes = det_off + up256((size_t)n_det * 2 * sizeof(double));
+  const size_t rec_bytes = (size_t)n_problems * sizeof(mpe_result);
+  const size_t match_words = n_lists * (size_t)n_markers;
+  const size_t m_off = up256(rec_bytes);
+  const size_t i_off = m_off + up256(match_words * sizeof(uint32_t));
+  const size_t back_bytes = i_off + (size_t)n_problems * sizeof(mpe_rig_init_info);
+  const size_t back_off = up256(in_bytes);
+  const size_t win_off = up256((size_t)n_chunks * MPE_RIG_INIT_KEY_BYTES);
+  const size_t run_off = win_off + up256((size_t)n_problems * MPE_RIG_INIT_KEY_BYTES);
+  const size_t rows_off = run_off + up256((size_t)n_chunks * sizeof(int));
+  const size_t work_bytes = rows_off + (size_t)n_problems * MPE_RIG_MAX_CAMERAS * MPE_MAX_MARKERS;
+  { const int rc = grow_mailbox(h, back_off + back_bytes); if (rc != MPE_OK) return rc; }
+  uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
+  std::memcpy(mb, cameras, cam_bytes);
+  std::memcpy(mb + mk_off, markers_xyz, (size_t)n_markers * 3 * sizeof(double));
+  std::memcpy(mb + tv_off, vote_tolerance, (size_t)n_cameras * sizeof(double));
+  std::memcpy(mb + ta_off, accept_tolerance, (size_t)n_cameras * sizeof(double));
+  int* hb = reinterpret_cast<int*>(mb + beg_off);
+  for (size_t i = 0; i <= n_lists; ++i) hb[i] = det_begin[i] - d0;
+  std::memcpy(mb + chk_off, chunk_begin.data(), chunk_begin.size() * sizeof(int));
+  if (n_det > 0) std::memcpy(mb + det_off, det_xy + (size_t)2 * d0, (size_t)n_det * 2 * sizeof(double));
+  HIP_TRY(h, h->frames.reserve(in_bytes));
+  HIP_TRY(h, h->results.reserve(back_bytes));
+  HIP_TRY(h, h->scratch.reserve(work_bytes));
+  uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
+  uint8_t* d_back = static_cast<uint8_t*>(h->results.p);
+  uint8_t* d_work = static_cast<uint8_t*>(h->scratch.p);
+  HIP_TRY(h, hipMemcpyAsync(d_in, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
+  RigInitDev d;
+  d.cams = reinterpret_cast<const mpe_rig_camera*>(d_in);
+  d.markers = reinterpret_cast<const double*>(d_in + mk_off);
+  d.det_xy = reinterpret_cast<const double*>(d_in + det_off);
+  d.tol_vote = reinterpret_cast<const double*>(d_in + tv_off);
+  d.tol_accept = reinterpret_cast<const double*>(d_in + ta_off);
+  d.det_begin = reinterpret_cast<const int*>(d_in + beg_off);
+  d.chunk_begin = reinterpret_cast<const int*>(d_in + chk_off);
+  d.n_cam = n_cameras, d.n_markers = n_markers, d.n_problems = n_problems, d.n_chunks = n_chunks;
+  d.max_rounds = opt.max_rounds, d.min_rows = opt.min_rows, d.min_markers = opt.min_markers, d.min_margin = opt.min_margin;
+  d.keys = reinterpret_cast<RigInitKey*>(d_work);
+  d.winner = reinterpret_cast<RigInitKey*>(d_work + win_off);
+  d.runners = reinterpret_cast<int*>(d_work + run_off);
+  d.win_rows = d_work + rows_off;
+  d.out = reinterpret_cast<mpe_result*>(d_back);
+  d.match = reinterpret_cast<uint32_t*>(d_back + m_off);
+  d.info = reinterpret_cast<mpe_rig_init_info*>(d_back + i_off);
+  RigLaunchTimer timer(h);
+  HIP_TRY(h, timer.begin());
+  HIP_TRY(h, launch_k_rig_init(d, h->stream));
+  HIP_TRY(h, timer.end());
+  ++h->rig_init_submits;
+  HIP_TRY(h, hipMemcpyAsync(mb + back_off, d_back, back_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  timer.read();
+  std::memcpy(out, mb + back_off, rec_bytes);
+  if (match_out) std::memcpy(match_out, mb + back_off + m_off, match_words * sizeof(uint32_t));
+  if (info_out) std::memcpy(info_out, mb + back_off + i_off, (size_t)n_problems * sizeof(mpe_rig_init_info));
   return MPE_OK;
 }
 

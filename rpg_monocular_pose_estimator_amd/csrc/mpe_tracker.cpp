@@ -572,6 +572,29 @@ int mpe_rig_track_trackers(mpe_tracker* const* ts, int n, const double* T_cam_ri
   return rig_out->status == MPE_FRAME_POSE ? 1 : 0;
 }
 
+int mpe_rig_init_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const mpe_rig_init_options* options,
+                          mpe_result* rig_out, uint32_t* match_out, mpe_rig_init_info* info_out) {
+  if (const int refused = rig_trackers_refused(ts, n, T_cam_rig && rig_out)) return refused;
+  mpe_handle* h = ts[0]->h;
+  // every tracker's image points of the frame, as mpe_rig_track_trackers takes them; initialise() votes with the
+  // back-projection tolerance, and so does this
+  std::vector<mpe_rig_camera> cams((size_t)n);
+  std::vector<int> det_begin((size_t)n + 1, 0);
+  std::vector<double> det_xy, tol((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const mpe_tracker* t = ts[i];
+    std::memcpy(cams[(size_t)i].K, t->K, sizeof(t->K));
+    std::memcpy(cams[(size_t)i].T_cam_rig, T_cam_rig + 16 * (size_t)i, 16 * sizeof(double));
+    det_xy.insert(det_xy.end(), t->det.begin(), t->det.end());
+    det_begin[(size_t)i + 1] = (int)det_xy.size() / 2;
+    tol[(size_t)i] = t->p.back_projection_pixel_tolerance;
+  }
+  const int rc = mpe_rig_init_batch(h, cams.data(), n, ts[0]->markers.data(), n_markers(ts[0]), det_begin.data(), det_xy.data(),
+                                    tol.data(), tol.data(), 1, options, rig_out, match_out, info_out);
+  if (rc != MPE_OK) return rc;
+  return rig_out->status == MPE_FRAME_POSE ? 1 : 0;
+}
+
 int mpe_rig_seed_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const int* seed, const double rig_pose[16],
                           double time, const double* rig_prev_pose, double prev_time) {
   if (!ts || n < 1 || n > MPE_RIG_MAX_CAMERAS || !T_cam_rig || !seed || !rig_pose) return MPE_ERR_ARG;
