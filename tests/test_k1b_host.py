@@ -414,3 +414,80 @@ def test_raw_frame_blur_equals_the_blur_of_the_thresholded_copy(host, orc):
         assert r >= 0, (it, rows, cols, thr, sigma)
         total += r
     assert total > 50000
+
+
+# ---- the shape filter at its edges and every distortion model (detection_parameter_cases.py) ---------------------------
+
+def _same_as_oracle(host, orc, img, kw, K, D, roi_xy, what):
+    """host_find_leds against orc.find_leds on the window at roi_xy of a padded image: same count, same order, dist_xy
+    and undist_xy equal as bytes."""
+    P = orc.make_params(**kw)
+    rows, cols = img.shape
+    ref_und, ref_dist = orc.find_leds(np.pad(img, ((roi_xy[1], 3), (roi_xy[0], 5))), P, K, D,
+                                      roi=(roi_xy[0], roi_xy[1], cols, rows))
+    und, dist = _host_find_leds(host, orc, img, P, K, D, roi_xy)
+    assert len(dist) == len(ref_dist), (what, len(dist), len(ref_dist))
+    assert dist.tobytes() == ref_dist.tobytes() and und.tobytes() == ref_und.tobytes(), what
+    return len(dist)
+
+
+def test_shape_filter_edges_on_the_host(host, orc):
+    """The four predicates of blob_filter exactly ON their edges (the statistic itself: kept; the next float64 towards
+    rejection: dropped) for every contour of the drawn-shape frame, with the other fields wide open, two mixed points and
+    the demo point; a ROI with an odd origin.  The count must also be the one the statistics predict, so a wrong oracle
+    and a wrong device source cannot agree by accident."""
+    import detection_parameter_cases as dpc
+    img = dpc.shape_frame()
+    stats = dpc.contour_statistics(orc, img)
+    K, D = synth.camera_for(*img.shape)
+    pts = dpc.parameter_points(stats)
+    assert len(pts) >= 2 * 24
+    for label, kw in pts:
+        n = _same_as_oracle(host, orc, img, dict(kw, threshold_value=dpc.THR, gaussian_sigma=dpc.SIGMA), K, D, (7, 5), label)
+        assert n == dpc.expected_count(stats, kw), (label, n)
+    # blobs of width 1 and of height 1: an integer half of 0, the statistic is 0 / 0 and never <= anything
+    thin = dpc.thin_frame()
+    tstats = dpc.contour_statistics(orc, thin, sigma=0.2)
+    for mc in (1e9, float("inf")):
+        kw = dict(dpc.OPEN, max_circular_distortion=mc)
+        n = _same_as_oracle(host, orc, thin, dict(kw, threshold_value=dpc.THR, gaussian_sigma=0.2), K, D, (3, 1), ("thin", mc))
+        assert n == dpc.expected_count(tstats, kw) == 1, (mc, n)
+
+
+def test_both_contour_phases_see_the_filter_edges(host, orc):
+    """cells_phase (the cell sums; island_record) and scan_window (the literal trace) on the drawn-shape mask, one island
+    window per shape, at a handful of edge points: the kept blobs agree, the ring (a hole) is the one island handed back
+    to the trace, the seven others are decided by the cell sums."""
+    from scipy import ndimage
+    import detection_parameter_cases as dpc
+    host.host_cells_vs_trace.restype = C.c_int
+    img = dpc.shape_frame()
+    stats = dpc.contour_statistics(orc, img)
+    _, mask = orc.blur_mask(img, dpc.THR, dpc.SIGMA)
+    mask = np.ascontiguousarray(mask > 0, np.uint8)
+    lab, n = ndimage.label(mask, structure=np.ones((3, 3), int))
+    wins = np.ascontiguousarray([[s[0].start, s[0].stop, s[1].start, s[1].stop] for s in ndimage.find_objects(lab)], np.int32)
+    assert n == len(stats) == 8
+    pts = dpc.parameter_points(stats)
+    pick = [p for p in pts if "@76.0" in p[0] or "0.5333" in p[0] or "1.6879" in p[0] or "0.5048" in p[0] or p[0] == "demo"]
+    assert len(pick) >= 9
+    for label, kw in pick:
+        shape = np.array([kw[f] for f in dpc.FIELDS])
+        fb = C.c_int(0)
+        r = host.host_cells_vs_trace(mask.ctypes.data_as(C.c_void_p), mask.shape[0], mask.shape[1],
+                                     wins.ctypes.data_as(C.c_void_p), len(wins), shape.ctypes.data_as(C.c_void_p), C.byref(fb))
+        assert r == 8 and fb.value == 1, (label, r, fb.value)
+
+
+def test_distortion_models_on_the_host(host, orc):
+    """undistort_point with 0, 4, 5, 8 and 12 coefficients and a skewed K (detection_parameter_cases.CAMERAS) against the
+    oracle on frames of spots, wide-open and demo filter, with and without a ROI origin."""
+    import detection_parameter_cases as dpc
+    n_blobs = 0
+    for c, (name, (K, D)) in enumerate(dpc.CAMERAS.items()):
+        rng = np.random.default_rng(40 + c)
+        for it in range(4):
+            img = dpc.spots_frame(rng, K, D)
+            kw = dict(dpc.OPEN) if it % 2 else {}
+            n_blobs += _same_as_oracle(host, orc, img, kw, K, D, (11, 3) if it < 2 else (0, 0), (name, it))
+    assert n_blobs >= 7 * 4 * 6, n_blobs

@@ -317,6 +317,71 @@ def test_undistort_inverts_distort(orc):
     assert np.abs(u - pts).max() < 0.05   # 5 fixed-point iterations, float32 output
 
 
+# A 15 x 11 grid of ideal pixel positions that covers the 752 x 480 image; what the camera sees of them is the forward
+# rational model written out in detection_parameter_cases.forward_rational.
+def _image_grid():
+    gx, gy = np.meshgrid(np.linspace(0, 751, 15), np.linspace(0, 479, 11))
+    return np.stack([gx.ravel(), gy.ravel()], 1)
+
+
+# largest |undistort(forward(p)) - p| (Euclidean, px) of the oracle over that grid, measured on the development machine
+# (five fixed-point iterations do not converge further; the corners decide):
+INVERSION_ERROR_PX = {"README": 0.0821, "D4": 0.0821, "D5": 0.1859, "D8": 0.2333, "D12": 0.2333}
+
+
+@pytest.mark.parametrize("name", ["D0", "README", "D4", "D5", "D8", "D12"])
+def test_undistort_with_0_4_5_8_coefficients(orc, name):
+    """cv::undistortPoints' rational model k1 k2 p1 p2 k3 k4 k5 k6 (led_detector.h:81: 4, 5 or 8 coefficients) in the
+    oracle: bit for bit the independent witness (tests/witness_pipeline.py) for every coefficient count, and the inverse
+    of the forward rational model written out in plain float64 to within TWICE the error measured for that camera
+    (INVERSION_ERROR_PX above: 0.082 px README and D4, 0.186 px D5, 0.233 px D8 and D12; no distortion: float32 rounding
+    alone).  Coefficients beyond the eighth are ignored."""
+    import detection_parameter_cases as dpc
+    import witness_pipeline
+    K, D = dpc.CAMERAS[name]
+    grid = _image_grid()
+    seen = dpc.forward_rational(grid, K, D).astype(np.float32)
+    und = orc.undistort_points(seen, K, D)
+    assert np.array_equal(und, witness_pipeline.undistort_points(seen, K, D))
+    err = float(np.linalg.norm(und - grid, axis=1).max())
+    print("inversion error", name, err)
+    assert err <= (2 * INVERSION_ERROR_PX[name] if len(D) else 1e-4), (name, err)
+    if name == "D12":
+        assert np.array_equal(und, orc.undistort_points(seen, K, dpc.D8))
+    if name == "D4":
+        assert np.array_equal(und, orc.undistort_points(seen, K, synth.README_D))   # README's k3 is 0.0
+
+
+def test_undistort_uses_every_coefficient_of_the_rational_model(orc):
+    """Zeroing any one of the eight coefficients of D8 moves some grid point by more than 0.1 px (k3 k4 k5 k6 alone:
+    2.2, 115, 8.3 and 0.35 px): an answer that matches the witness has used that coefficient."""
+    import detection_parameter_cases as dpc
+    K = synth.README_K
+    seen = dpc.forward_rational(_image_grid(), K, dpc.D8).astype(np.float32)
+    und = orc.undistort_points(seen, K, dpc.D8)
+    for i in range(8):
+        D = dpc.D8.copy()
+        D[i] = 0.0
+        assert np.linalg.norm(orc.undistort_points(seen, K, D) - und, axis=1).max() > 0.1, i
+
+
+def test_distort_points_ignores_k4_k5_k6(orc):
+    """LEDDetector::distortPoints is polynomial only (led_detector.cpp:190-194): k1 k2 p1 p2 k3, whatever else D holds;
+    missing coefficients are zero.  Oracle, witness and the library's host arithmetic agree bit for bit."""
+    import detection_parameter_cases as dpc
+    import witness_pipeline
+    import rpg_monocular_pose_estimator_amd as mpe
+    grid = _image_grid().astype(np.float32)
+    for name, (K, D) in dpc.CAMERAS.items():
+        d = orc.distort_points(grid, K, D)
+        assert np.array_equal(d, np.array(witness_pipeline.distort_points(grid, K, D), np.float32)), name
+        assert np.array_equal(d, mpe.distort_points(grid, K, D)), name
+        assert np.array_equal(d, orc.distort_points(grid, K, (list(D) + [0.0] * 5)[:5])), name
+        roi = orc.determine_roi(grid[20:25], 480, 752, 20, K, D)
+        assert roi == witness_pipeline.determine_roi(grid[20:25], 480, 752, 20, K, D) == \
+            tuple(mpe.determine_roi(grid[20:25], 480, 752, 20, K, D)), name
+
+
 def test_roi_detection_offsets(orc):
     d = synth.make_frames("C2", 1, seed=5)
     P = orc.make_params()

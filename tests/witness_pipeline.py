@@ -524,18 +524,21 @@ def find_leds(img, thr, sigma, min_area, max_area, max_wh, max_circ, K, D, roi=N
 
 
 def undistort_points(pts, K, D):
-    """cv::undistortPoints(src, dst, K, D, noArray(), K): 5 fixed-point iterations, float32 out (SURVEY A.1.7)."""
+    """cv::undistortPoints(src, dst, K, D, noArray(), K): 5 fixed-point iterations, float32 out (SURVEY A.1.7).
+    D holds 0 to 8 coefficients k1 k2 p1 p2 k3 k4 k5 k6 of the rational model (led_detector.h:81 documents 4, 5 or 8);
+    missing ones are zero, anything beyond the eighth is ignored.  With k4 = k5 = k6 = 0 the numerator below is exactly
+    1.0: the five-coefficient results are what they were."""
     K = np.asarray(K, float).reshape(3, 3)
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     d = list(np.asarray(D, float).reshape(-1)) + [0.0] * 8
-    k1, k2, p1, p2, k3 = d[:5]
+    k1, k2, p1, p2, k3, k4, k5, k6 = d[:8]
     out = np.zeros((len(pts), 2), np.float32)
     for i, (u, v) in enumerate(np.asarray(pts, np.float64)):
         x0 = x = (u - cx) * (1.0 / fx)  # OpenCV multiplies by ifx = 1 / fx
         y0 = y = (v - cy) * (1.0 / fy)
         for _ in range(5 if len(np.asarray(D).reshape(-1)) else 0):
             r2 = x * x + y * y
-            icd = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+            icd = (1 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
             dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
             dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
             x = (x0 - dx) * icd
@@ -600,10 +603,12 @@ def logarithm_map(T):
 
 
 def distort_points(pts, K, D):
-    """LEDDetector::distortPoints, led_detector.cpp:181-224: float32 points in, computed in double, float32 out."""
+    """LEDDetector::distortPoints, led_detector.cpp:181-224: float32 points in, computed in double, float32 out.
+    D holds 0 to 8 coefficients (missing ones are zero); the reference's quirk is kept: the model here is polynomial
+    only, k1 k2 p1 p2 k3, and k4 k5 k6 are ignored (led_detector.cpp:190-194)."""
     K = np.asarray(K, float).reshape(3, 3)
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
-    k1, k2, p1, p2, k3 = [float(v) for v in np.asarray(D, float).reshape(-1)[:5]]
+    k1, k2, p1, p2, k3 = ([float(v) for v in np.asarray(D, float).reshape(-1)] + [0.0] * 5)[:5]
     out = []
     for (px, py) in pts:
         px, py = float(np.float32(px)), float(np.float32(py))
