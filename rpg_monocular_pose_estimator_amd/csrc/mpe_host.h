@@ -328,7 +328,27 @@ __attribute__((visibility("hidden"))) hipError_t launch_gather_rois_encoded(cons
 // below its length — the submission builds both; k_gather_rois_formats).  sensor: the table holds a YUV or a Bayer entry
 __attribute__((visibility("hidden"))) hipError_t launch_gather_rois_formats(const GatherItem* tab, const GatherFormat* fmts, int n, uint8_t* dst,
                                       const FrameGeom& g, bool sensor, hipStream_t s);
-// the text of mpe_last_error, for mpe_tracker.cpp (which sees only the C ABI and declares this itself; mpe_options.cpp)
+// Where the pixels of the n items of a lock-step submission are and what they look like: the one description behind
+// every tracked entry.  formats holds distinct formats (same_image_format, mpe_pixel.h), each checked by the entry
+// (check_image_format); item i is an image of formats[item_format[i]].  One format, or several: that decides the gather
+// (submit_slots, mpe_track_abi.cpp), so a caller whose items share a format passes that format alone; a format without
+// items among several costs its entry of the format table and nothing else.
+struct SlotPixels {
+  bool on_device;                   // items[i].img are device pointers: a kernel gathers the ROIs; else the host packs them
+  const int* item_format;           // n indices into formats, or null: every item is of formats[0]
+  const mpe_image_format* formats;
+  int n_formats;
+  const mpe_image_format& of(int i) const { return formats[item_format ? item_format[i] : 0]; }
+};
+// What every tracked submit entry does behind its own argument condition and the format check (mpe_track_abi.cpp): the
+// usage errors that need the items (no submission in flight, the set-ups, every item's set-up index — item_setup null:
+// set-up 0 — and its ROI against its own format), all before any device work; then the handle is entered, device images
+// are checked against their allocations, and the slots are submitted.  n == 0: MPE_OK, nothing submitted.  wide: staged
+// for run_wide_slots, nothing launched behind the gather and nothing left pending.
+__attribute__((visibility("hidden"))) int submit_tracked(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                                                         const mpe_track_setup* setups, int n_setups, const SlotPixels& px,
+                                                         bool wide);
+// the text of mpe_last_error (mpe_options.cpp)
 void set_error(mpe_handle* h, const char* what);
 }  // namespace mpe_host
 using namespace mpe_host;

@@ -60,6 +60,58 @@ __host__ __device__ inline int encoding_bytes_per_pixel(int encoding) {
   }
 }
 
+// ---- an image format (mpe_image_format: rows, cols, stride in source bytes, encoding, byte order) on the host: what the
+// tracked entries ask of one, stated once for mpe_track_abi.cpp and mpe_tracker.cpp.  No handle, no HIP call.
+
+// the bytes from an image's first pixel to the last pixel of its last row (rows >= 1, a known encoding): what a device
+// allocation must hold of it, and where the gathers stop reading
+inline size_t image_extent(const mpe_image_format& f) {
+  return (size_t)(f.rows - 1) * f.stride_bytes + (size_t)f.cols * (size_t)encoding_bytes_per_pixel(f.encoding);
+}
+
+// two formats name the same images: size, stride, encoding and — for mono16, which alone reads it — the byte order
+inline bool same_image_format(const mpe_image_format& a, const mpe_image_format& b) {
+  return a.rows == b.rows && a.cols == b.cols && a.stride_bytes == b.stride_bytes && a.encoding == b.encoding &&
+         (a.encoding != MPE_ENC_MONO16 || (a.src_big_endian != 0) == (b.src_big_endian != 0));
+}
+
+// Why images of a format are refused: the code and the text for mpe_last_error, or {MPE_OK, null}.  Three rules, each
+// stated once; an entry asks them in order and the first that fails answers.
+struct FormatRefusal {
+  int code;
+  const char* msg;
+};
+// the encoding is one the library knows and can decode from where the frames are
+inline FormatRefusal refuse_encoding(int encoding, bool on_device) {
+  if (!encoding_bytes_per_pixel(encoding)) return {MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)"};
+  if (!on_device && encoding_kind(encoding) != PIX_PLAIN)  // (what these codes answered before they existed)
+    return {MPE_ERR_UNSUPPORTED, "encoding not supported for host frames (Bayer and YUV: device frames)"};
+  return {MPE_OK, nullptr};
+}
+// host frames are packed, not decoded (a rule for formats that have images in the call)
+inline FormatRefusal refuse_host_encoding(int encoding, bool on_device) {
+  if (!on_device && encoding != MPE_ENC_MONO8)
+    return {MPE_ERR_ARG, "host frames are mono8 (the encodings are decoded from device frames)"};
+  return {MPE_OK, nullptr};
+}
+// a size, and a stride that holds a row (of a known encoding)
+inline FormatRefusal refuse_size(const mpe_image_format& f) {
+  if (f.rows < 1 || f.cols < 1 || f.stride_bytes < (size_t)f.cols * (size_t)encoding_bytes_per_pixel(f.encoding))
+    return {MPE_ERR_ARG, "bad argument"};
+  return {MPE_OK, nullptr};
+}
+// The two orders the entries ask them in.  check_format_shape: the format as such, with or without images in the call —
+// encoding, then size.  check_image_format: a format that has images — the same, then the host rule.
+// (mpe_track_step_batch_wide alone asks the host rule before the size: mpe_track_abi.cpp.)
+inline FormatRefusal check_format_shape(const mpe_image_format& f, bool on_device) {
+  const FormatRefusal r = refuse_encoding(f.encoding, on_device);
+  return r.code != MPE_OK ? r : refuse_size(f);
+}
+inline FormatRefusal check_image_format(const mpe_image_format& f, bool on_device) {
+  const FormatRefusal r = check_format_shape(f, on_device);
+  return r.code != MPE_OK ? r : refuse_host_encoding(f.encoding, on_device);
+}
+
 // which of a YUV 4:2:2 pixel's two source bytes is its Y: 1 for yuv422 (U Y V Y), 0 for yuv422_yuy2 (Y U Y V)
 __host__ __device__ inline int yuv_y_byte(int encoding) { return encoding == MPE_ENC_YUV422 ? 1 : 0; }
 

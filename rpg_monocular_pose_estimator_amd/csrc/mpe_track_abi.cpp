@@ -1,10 +1,11 @@
 // mpe_track_abi.cpp — host side of libmpe_hip.so, part 3 (see mpe_host.h): one tracked frame (mpe_track_step) and the
 // lock-step time step of N camera streams (mpe_track_step_batch[_setups][_device[_encoded]][_submit / _collect / _cancel],
 // mpe_track_step_batch_formats[_submit] for streams that differ in image size, stride and encoding); the
-// per-stream state machine on top of them is mpe_tracker.cpp.  Every entry checks its own arguments and then makes the
-// same submission (submit_slots): a uniform batch is the submission of one set-up, a tracked frame a batch of one, and
-// frames in device memory differ only in where the ROI slots come from (a gather kernel instead of a host copy; for
-// frames in the camera's own encoding, a gather kernel that decodes).
+// per-stream state machine on top of them is mpe_tracker.cpp.  Every entry checks its own arguments and the image format
+// it was given (check_image_format, mpe_pixel.h), describes where the pixels are and what they look like in one
+// SlotPixels (mpe_host.h) and then makes the same submission (submit_tracked: the checks that need the items, then
+// submit_slots): a uniform batch is the submission of one set-up and one format, a tracked frame a batch of one, and the
+// description alone decides where the ROI slots come from — a host copy or one of three gather kernels.
 #include "mpe_host.h"
 #include "mpe_gather.h"
 
@@ -67,16 +68,14 @@ void pack_roi(uint8_t* slot, const FrameGeom& g, const mpe_track_item& it, size_
 // stands between a caller's mistake and a GPU fault.  Each distinct allocation is looked up once per call (the frames
 // of N streams usually sit in one or a few).  (static, as prepare_setups below: inside extern "C" the unnamed namespace
 // alone does not keep a name out of the library's exports, and these two are no part of them)
-// item_bytes (n values, or null: img_bytes for all): every item's OWN image extent.
-static int check_device_images(mpe_handle* h, const mpe_track_item* items, int n, size_t img_bytes,
-                               const size_t* item_bytes = nullptr) {
+static int check_device_images(mpe_handle* h, const mpe_track_item* items, int n, const SlotPixels& px) {
   struct Span {
     uintptr_t lo, hi;
   };
   std::vector<Span> ok;
   for (int i = 0; i < n; ++i) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(items[i].img);
-    if (item_bytes) img_bytes = item_bytes[i];
+    const size_t img_bytes = image_extent(px.of(i));
     bool known = false;
     for (const Span& s : ok) known |= a >= s.lo && a + img_bytes <= s.hi;
     if (known) continue;
@@ -160,33 +159,26 @@ int track_range_chain(mpe_handle* h, const mpe_handle::PendingTrack::Range& r, i
 // nearest-neighbour correspondences from the stream's predicted pixels, validate, refine) runs them, and every rare
 // path (track_fused 0, set-ups of more than 8 markers, the re-run of a range that overflowed the small blob tier) is
 // the chain of kernels over a range with its own parameters.  One copy brings the N records back; _collect un-permutes
-// them.  Where the pixels are is the one thing that varies: host frames are packed into the staging memory (pack_roi)
-// and travel with the header; of device frames (img_bytes each: an image ends with the last pixel of its last row) the
-// header carries a gather table instead and k_gather_rois writes the same slot bytes on the device, in front of
-// everything that reads them; of device frames in the camera's own encoding (bgr8 .. mono16; stride_bytes and img_bytes
-// in source bytes, the ROIs in pixels) k_gather_rois_encoded writes them, decoding what it gathers — the slots are mono8
-// whatever the source was, so nothing behind the gather, the overflow re-run in _collect included, knows the encoding.
-// The caller has checked the arguments and entered the handle.
+// them.  The caller has checked the arguments and entered the handle.
+// Where the pixels are is the one thing that varies, and px (SlotPixels, mpe_host.h) says it.  The slots are mono8
+// whatever the source was, so nothing behind them, the overflow re-run in _collect included, knows the source:
+//   host frames                          pack_roi with the item's own stride; the slots travel with the header
+//   device frames, one format, mono8     the header carries a gather table, k_gather_rois writes the same slot bytes on
+//                                        the device, in front of everything that reads them
+//   device frames, one other format      k_gather_rois_encoded, which decodes what it gathers (stride and extent in
+//                                        source bytes, the ROIs in pixels)
+//   device frames, two or more formats   the header carries the format table behind the gather table and
+//                                        k_gather_rois_formats decodes every item by its own entry
+// An image ends with the last pixel of its last row (image_extent): the extent check_device_images has checked is the
+// one every gather is given.  With two or more formats the slots of a set-up range are ordered by format (stable), so
+// the gather's branch on the format diverges only in the waves that hold a slot boundary between two formats; with one
+// format the slot order is that of the items.
 // wide (mpe_track_step_batch_wide): the same slots, header and gather, nothing launched behind them — no range is fused,
 // the header also carries one identity work-list per range for the general blob tier, the record area is sized for
 // WideTrackRecords, and the submission is not left pending: run_wide_slots works it off synchronously.
-// formats (mpe_track_step_batch_formats): every item has an image format of its own — fm->item_format[i] indexes
-// fm->formats, the distinct formats of the submission.  Host frames are packed with the item's stride; of device frames
-// the header carries the format table behind the gather table and k_gather_rois_formats decodes every item by its own
-// entry.  Within a set-up range the slots are then ordered by format (stable), so the gather's branch on the format
-// diverges only in the waves that hold a slot boundary between two formats.
-enum PixelSource { kHostFrames, kDeviceFrames, kEncodedDeviceFrames, kFormatDeviceFrames };
-struct SlotFormats {
-  const int* item_format;           // n indices into formats
-  const mpe_image_format* formats;  // distinct, checked
-  int n_formats;
-};
-
 int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, const FrameGeom& g,
-                 size_t stride_bytes, const TrackSetup* setups, int n_setups, PixelSource source = kHostFrames,
-                 size_t img_bytes = 0, int encoding = MPE_ENC_MONO8, int big_endian = 0, bool wide = false,
-                 const SlotFormats* fm = nullptr) {
-  const bool on_device = source != kHostFrames;
+                 const TrackSetup* setups, int n_setups, const SlotPixels& px, bool wide) {
+  const bool on_device = px.on_device, format_table = px.on_device && px.n_formats > 1;
   mpe_handle::PendingTrack& pt = h->pending_track;
   pt.t_in = h->track_profile ? clk::now() : clk::time_point();
   auto setup_of = [item_setup](int i) { return item_setup ? item_setup[i] : 0; };
@@ -213,13 +205,13 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     const int r = range_of[(size_t)setup_of(i)];
     pt.perm[(size_t)(pt.ranges[(size_t)r].begin + fill[(size_t)r]++)] = i;
   }
-  if (fm)
+  if (px.n_formats > 1)
     for (const mpe_handle::PendingTrack::Range& r : pt.ranges)
       std::stable_sort(pt.perm.begin() + r.begin, pt.perm.begin() + r.begin + r.count,
-                       [fm](int a, int b) { return fm->item_format[a] < fm->item_format[b]; });
-  // [predictions | windows | set-up table | slot -> set-up | gather table (device frames) | format table (device frames
-  // of several formats) | ROI slots] in slot order; one
-  // H2D copy carries what the host has of it: all of it, or the header in front of the slots.  The set-up table only for
+                       [&px](int a, int b) { return px.item_format[a] < px.item_format[b]; });
+  // [predictions | windows | set-up table | slot -> set-up | work lists (wide) | gather table (device frames) | format
+  // table (device frames of several formats) | ROI slots] in slot order; one H2D copy carries what the host has of it:
+  // all of it, or the header in front of the slots.  The set-up table only for
   // a launch of two or more set-ups: one set-up goes as kernel arguments (the table instantiation is 5.6 % slower)
   const bool table = fused_setups >= 2;
   const size_t slot = (size_t)g.rows * g.pitch;
@@ -232,7 +224,7 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   const size_t gat_off = list_off + list_bytes;
   const size_t fmt_off = gat_off + (on_device ? (size_t)n * sizeof(GatherItem) : 0);
   const size_t head_bytes =  // (a multiple of 16: the slots' alignment)
-      fmt_off + (source == kFormatDeviceFrames ? (size_t)fm->n_formats * sizeof(GatherFormat) : 0);
+      fmt_off + (format_table ? (size_t)px.n_formats * sizeof(GatherFormat) : 0);
   const size_t in_bytes = head_bytes + (size_t)n * slot;
   const size_t staged_bytes = on_device ? head_bytes : in_bytes;
   const size_t rec_bytes = wide ? WideTrackRecords::bytes(n) : TrackRecords::bytes(n);
@@ -258,6 +250,7 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     }
   }
   const double qnan = std::nan("");
+  bool sensor_formats = false;  // an item of the format table is a YUV or a Bayer image
   for (int k = 0; k < n; ++k) {
     const int i = pt.perm[(size_t)k];
     const mpe_track_item& it = items[i];
@@ -270,20 +263,17 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
     wins[4 * k + 2] = it.roi_x;
     wins[4 * k + 3] = it.roi_y;
     if (on_device)
-      gat[k] = GatherItem{it.img, it.roi_x, it.roi_y, it.roi_w, it.roi_h, k, fm ? fm->item_format[i] : 0};
+      gat[k] = GatherItem{it.img, it.roi_x, it.roi_y, it.roi_w, it.roi_h, k, px.item_format ? px.item_format[i] : 0};
     else
-      pack_roi(mb + head_bytes + (size_t)k * slot, g, it, fm ? fm->formats[fm->item_format[i]].stride_bytes : stride_bytes);
+      pack_roi(mb + head_bytes + (size_t)k * slot, g, it, px.of(i).stride_bytes);
+    if (format_table) sensor_formats |= encoding_kind(px.of(i).encoding) != PIX_PLAIN;
   }
-  bool sensor_formats = false;  // the table holds a YUV or a Bayer entry
-  if (source == kFormatDeviceFrames) {
+  if (format_table) {
     GatherFormat* tab = reinterpret_cast<GatherFormat*>(mb + fmt_off);
-    for (int f = 0; f < fm->n_formats; ++f) {
-      const mpe_image_format& mf = fm->formats[f];
-      const int bpp = encoding_bytes_per_pixel(mf.encoding);
+    for (int f = 0; f < px.n_formats; ++f) {
+      const mpe_image_format& mf = px.formats[f];
       const int kind = encoding_kind(mf.encoding);
-      sensor_formats |= kind != PIX_PLAIN;
-      tab[f] = GatherFormat{(uint64_t)mf.stride_bytes,
-                            (uint64_t)((size_t)(mf.rows - 1) * mf.stride_bytes + (size_t)mf.cols * (size_t)bpp), bpp,
+      tab[f] = GatherFormat{(uint64_t)mf.stride_bytes, (uint64_t)image_extent(mf), encoding_bytes_per_pixel(mf.encoding),
                             mf.encoding == MPE_ENC_RGB8 || mf.encoding == MPE_ENC_RGBA8,
                             mf.encoding == MPE_ENC_MONO16 && mf.src_big_endian, kind};
       if (kind == PIX_YUV) tab[f].big_endian = yuv_y_byte(mf.encoding);
@@ -315,16 +305,16 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   pt.d_wins = d_in + pred_bytes;
   pt.d_pix = d_in + head_bytes;
   pt.d_list = reinterpret_cast<const int*>(d_in + list_off);
-  if (source == kDeviceFrames)
-    HIP_TRY(h, launch_gather_rois(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g, stride_bytes,
-                                  img_bytes, h->stream));
-  else if (source == kEncodedDeviceFrames)
-    HIP_TRY(h, launch_gather_rois_encoded(reinterpret_cast<const GatherItem*>(d_in + gat_off), n, d_in + head_bytes, g,
-                                          stride_bytes, img_bytes, encoding, big_endian, h->stream));
-  else if (source == kFormatDeviceFrames)
-    HIP_TRY(h, launch_gather_rois_formats(reinterpret_cast<const GatherItem*>(d_in + gat_off),
-                                          reinterpret_cast<const GatherFormat*>(d_in + fmt_off), n, d_in + head_bytes, g,
+  const GatherItem* d_gat = reinterpret_cast<const GatherItem*>(d_in + gat_off);
+  const mpe_image_format& f0 = px.formats[0];
+  if (format_table)
+    HIP_TRY(h, launch_gather_rois_formats(d_gat, reinterpret_cast<const GatherFormat*>(d_in + fmt_off), n, d_in + head_bytes, g,
                                           sensor_formats, h->stream));
+  else if (on_device && f0.encoding == MPE_ENC_MONO8)
+    HIP_TRY(h, launch_gather_rois(d_gat, n, d_in + head_bytes, g, f0.stride_bytes, image_extent(f0), h->stream));
+  else if (on_device)
+    HIP_TRY(h, launch_gather_rois_encoded(d_gat, n, d_in + head_bytes, g, f0.stride_bytes, image_extent(f0), f0.encoding,
+                                          f0.src_big_endian ? 1 : 0, h->stream));
   if (wide) {
     h->pending_track_rec = host_rec;  // (for run_wide_slots, which follows at once: nothing stays pending)
     return MPE_OK;
@@ -360,14 +350,13 @@ int submit_slots(mpe_handle* h, const mpe_track_item* items, const int* item_set
   return MPE_OK;
 }
 
-// What the _setups entries (host and device frames) check behind their own argument condition, every usage error before
-// any device work: no submission in flight, the set-ups, every item's set-up index and ROI (item_setup null: set-up 0);
-// then the slot geometry g and the prepared parameters of the set-ups that have streams.  n == 0: MPE_OK with nothing
-// prepared — there is nothing to submit.  fm: every item's ROI against its OWN image, fm->formats[fm->item_format[i]]
-// (rows and cols are not read).
-static int prepare_setups(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows, int cols,
-                          const mpe_track_setup* setups, int n_setups, FrameGeom& g, std::vector<TrackSetup>& prep,
-                          const SlotFormats* fm = nullptr) {
+// The usage errors of a submission that need its items, every one before any device work: no submission in flight, the
+// set-ups, every item's set-up index (item_setup null: set-up 0) and its ROI against its own format; then the slot
+// geometry g and the prepared parameters of the set-ups that have streams.  n == 0: MPE_OK with nothing prepared — there
+// is nothing to submit.
+static int prepare_setups(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                          const mpe_track_setup* setups, int n_setups, const SlotPixels& px, FrameGeom& g,
+                          std::vector<TrackSetup>& prep) {
   if (h->pending_track_n) return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
   for (int s = 0; s < n_setups; ++s) {
     const mpe_track_setup& su = setups[s];
@@ -380,11 +369,8 @@ static int prepare_setups(mpe_handle* h, const mpe_track_item* items, const int*
   for (int i = 0; i < n; ++i) {
     const int s = item_setup ? item_setup[i] : 0;
     if (s < 0 || s >= n_setups) return fail(h, MPE_ERR_ARG, "set-up index out of range");
-    if (fm) {
-      rows = fm->formats[fm->item_format[i]].rows;
-      cols = fm->formats[fm->item_format[i]].cols;
-    }
-    if (!items[i].img || !roi_inside(items[i], rows, cols)) return fail(h, MPE_ERR_ARG, "ROI outside the image");
+    if (!items[i].img || !roi_inside(items[i], px.of(i).rows, px.of(i).cols))
+      return fail(h, MPE_ERR_ARG, "ROI outside the image");
     used[(size_t)s] = 1;
     rmax = std::max(rmax, items[i].roi_h);
     wmax = std::max(wmax, items[i].roi_w);
@@ -403,6 +389,22 @@ static int prepare_setups(mpe_handle* h, const mpe_track_item* items, const int*
 }
 }  // namespace
 
+}  // extern "C"
+
+int mpe_host::submit_tracked(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
+                             const mpe_track_setup* setups, int n_setups, const SlotPixels& px, bool wide) {
+  FrameGeom g;
+  std::vector<TrackSetup> prep;
+  int rc = prepare_setups(h, items, item_setup, n, setups, n_setups, px, g, prep);
+  if (rc != MPE_OK || n == 0) return rc;
+  ENTER(h);
+  if (px.on_device && (rc = check_device_images(h, items, n, px)) != MPE_OK) return rc;
+  return submit_slots(h, items, item_setup, n, g, prep.data(), n_setups, px, wide);
+}
+
+extern "C" {
+
+// (the one entry that takes its set-up as plain arguments, and answers for it with codes of its own)
 int mpe_track_step_batch_submit(mpe_handle* h, const mpe_track_item* items, int n, int rows, int cols,
                                 size_t stride_bytes, const mpe_params* p, const double K[9], const double* D, int nD,
                                 const double* markers_xyz, int n_markers) {
@@ -422,19 +424,17 @@ int mpe_track_step_batch_submit(mpe_handle* h, const mpe_track_item* items, int 
   if (make_detect_params(p, K, D, nD, 0, 0, su.dp)) return fail(h, MPE_ERR_ARG, "gaussian_sigma must be in (0, 6]");
   if (make_solve_params(h, p, markers_xyz, n_markers, K, su.sp)) return fail(h, MPE_ERR_UNSUPPORTED, "n_markers > MPE_MAX_MARKERS");
   su.nn_tol = p->nearest_neighbour_pixel_tolerance;
-  return submit_slots(h, items, nullptr, n, g, stride_bytes, &su, 1);
+  const mpe_image_format f = {rows, cols, stride_bytes, MPE_ENC_MONO8, 0};
+  return submit_slots(h, items, nullptr, n, g, &su, 1, SlotPixels{false, nullptr, &f, 1}, false);
 }
 
 int mpe_track_step_batch_setups_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows,
                                        int cols, size_t stride_bytes, const mpe_track_setup* setups, int n_setups) {
   // every usage error before any device work
   if (!h || !items || !item_setup || n < 0 || !setups || n_setups < 1) return fail(h, MPE_ERR_ARG, "bad argument");
-  FrameGeom g;
-  std::vector<TrackSetup> prep;
-  const int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
-  if (rc != MPE_OK || n == 0) return rc;
-  ENTER(h);
-  return submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups);
+  // (host frames are mono8 by this entry's signature; a size that holds no pixels fails as a ROI outside the image)
+  const mpe_image_format f = {rows, cols, stride_bytes, MPE_ENC_MONO8, 0};
+  return submit_tracked(h, items, item_setup, n, setups, n_setups, SlotPixels{false, nullptr, &f, 1}, false);
 }
 
 int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
@@ -444,14 +444,8 @@ int mpe_track_step_batch_setups_device_submit(mpe_handle* h, const mpe_track_ite
   if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || rows < 1 || cols < 1 ||
       stride_bytes < (size_t)cols)
     return fail(h, MPE_ERR_ARG, "bad argument");
-  FrameGeom g;
-  std::vector<TrackSetup> prep;
-  int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
-  if (rc != MPE_OK || n == 0) return rc;
-  ENTER(h);
-  const size_t img_bytes = (size_t)(rows - 1) * stride_bytes + (size_t)cols;
-  if ((rc = check_device_images(h, items, n, img_bytes)) != MPE_OK) return rc;
-  return submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups, kDeviceFrames, img_bytes);
+  const mpe_image_format f = {rows, cols, stride_bytes, MPE_ENC_MONO8, 0};
+  return submit_tracked(h, items, item_setup, n, setups, n_setups, SlotPixels{true, nullptr, &f, 1}, false);
 }
 
 int mpe_track_step_batch_setups_device(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n, int rows,
@@ -470,20 +464,11 @@ int mpe_track_step_batch_setups_device_encoded_submit(mpe_handle* h, const mpe_t
   // every usage error before any device work: those of mpe_track_step_batch_setups_device_submit, and the encoding
   if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || rows < 1 || cols < 1)
     return fail(h, MPE_ERR_ARG, "bad argument");
-  const size_t bpp = (size_t)encoding_bytes_per_pixel(encoding);
-  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)");
-  if (stride_bytes < (size_t)cols * bpp) return fail(h, MPE_ERR_ARG, "bad argument");
-  if (encoding == MPE_ENC_MONO8)  // nothing to decode: the mono8 submission and k_gather_rois
-    return mpe_track_step_batch_setups_device_submit(h, items, item_setup, n, rows, cols, stride_bytes, setups, n_setups);
-  FrameGeom g;
-  std::vector<TrackSetup> prep;
-  int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
-  if (rc != MPE_OK || n == 0) return rc;
-  ENTER(h);
-  const size_t img_bytes = (size_t)(rows - 1) * stride_bytes + (size_t)cols * bpp;
-  if ((rc = check_device_images(h, items, n, img_bytes)) != MPE_OK) return rc;
-  return submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups, kEncodedDeviceFrames, img_bytes,
-                      encoding, src_big_endian ? 1 : 0);
+  const mpe_image_format f = {rows, cols, stride_bytes, encoding, src_big_endian};
+  const FormatRefusal no = check_image_format(f, true);
+  if (no.code != MPE_OK) return fail(h, no.code, no.msg);
+  // (MPE_ENC_MONO8: nothing to decode — the submission of mpe_track_step_batch_setups_device_submit, and k_gather_rois)
+  return submit_tracked(h, items, item_setup, n, setups, n_setups, SlotPixels{true, nullptr, &f, 1}, false);
 }
 
 int mpe_track_step_batch_setups_device_encoded(mpe_handle* h, const mpe_track_item* items, const int* item_setup, int n,
@@ -498,14 +483,6 @@ int mpe_track_step_batch_setups_device_encoded(mpe_handle* h, const mpe_track_it
   return mpe_track_step_batch_collect(h, dets_out, corr_out, out);
 }
 
-namespace {
-// two formats name the same images: size, stride, encoding and — for mono16, which alone reads it — the byte order
-bool same_format(const mpe_image_format& a, const mpe_image_format& b) {
-  return a.rows == b.rows && a.cols == b.cols && a.stride_bytes == b.stride_bytes && a.encoding == b.encoding &&
-         (a.encoding != MPE_ENC_MONO16 || (a.src_big_endian != 0) == (b.src_big_endian != 0));
-}
-}  // namespace
-
 int mpe_track_step_batch_formats_submit(mpe_handle* h, const mpe_track_item* items, const int* item_setup,
                                         const int* item_format, int n, const mpe_image_format* formats, int n_formats,
                                         int frames_on_device, const mpe_track_setup* setups, int n_setups) {
@@ -514,12 +491,8 @@ int mpe_track_step_batch_formats_submit(mpe_handle* h, const mpe_track_item* ite
       (!item_format && n_formats != 1))
     return fail(h, MPE_ERR_ARG, "bad argument");
   for (int f = 0; f < n_formats; ++f) {
-    const size_t bpp = (size_t)encoding_bytes_per_pixel(formats[f].encoding);
-    if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)");
-    if (!frames_on_device && encoding_kind(formats[f].encoding) != PIX_PLAIN)  // (what these codes answered before)
-      return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported for host frames (Bayer and YUV: device frames)");
-    if (formats[f].rows < 1 || formats[f].cols < 1 || formats[f].stride_bytes < (size_t)formats[f].cols * bpp)
-      return fail(h, MPE_ERR_ARG, "bad argument");
+    const FormatRefusal no = check_format_shape(formats[f], frames_on_device != 0);
+    if (no.code != MPE_OK) return fail(h, no.code, no.msg);
   }
   // the distinct formats that have items, in order of first use, and every item's index among them
   std::vector<mpe_image_format> used;
@@ -528,41 +501,18 @@ int mpe_track_step_batch_formats_submit(mpe_handle* h, const mpe_track_item* ite
     const int f = item_format ? item_format[i] : 0;
     if (f < 0 || f >= n_formats) return fail(h, MPE_ERR_ARG, "format index out of range");
     if (dense[(size_t)f] < 0) {
-      if (!frames_on_device && formats[f].encoding != MPE_ENC_MONO8)
-        return fail(h, MPE_ERR_ARG, "host frames are mono8 (the encodings are decoded from device frames)");
+      const FormatRefusal no = check_image_format(formats[f], frames_on_device != 0);  // (now that it has an item)
+      if (no.code != MPE_OK) return fail(h, no.code, no.msg);
       size_t k = 0;
-      while (k < used.size() && !same_format(used[k], formats[f])) ++k;
+      while (k < used.size() && !same_image_format(used[k], formats[f])) ++k;
       if (k == used.size()) used.push_back(formats[f]);
       dense[(size_t)f] = (int)k;
     }
     item_dense[(size_t)i] = dense[(size_t)f];
   }
-  if (used.size() <= 1) {  // one format (or no item): the entry of that format, unchanged
-    const mpe_image_format& f = used.empty() ? formats[0] : used[0];
-    if (frames_on_device)
-      return mpe_track_step_batch_setups_device_encoded_submit(h, items, item_setup, n, f.rows, f.cols, f.stride_bytes,
-                                                               f.encoding, f.src_big_endian, setups, n_setups);
-    const std::vector<int> zero((size_t)n + 1, 0);  // (the host entry wants an index per item)
-    return mpe_track_step_batch_setups_submit(h, items, item_setup ? item_setup : zero.data(), n, f.rows, f.cols,
-                                              f.stride_bytes, setups, n_setups);
-  }
-  const SlotFormats fm = {item_dense.data(), used.data(), (int)used.size()};
-  FrameGeom g;
-  std::vector<TrackSetup> prep;
-  int rc = prepare_setups(h, items, item_setup, n, 0, 0, setups, n_setups, g, prep, &fm);
-  if (rc != MPE_OK) return rc;
-  ENTER(h);
-  if (!frames_on_device)
-    return submit_slots(h, items, item_setup, n, g, 0, prep.data(), n_setups, kHostFrames, 0, MPE_ENC_MONO8, 0, false, &fm);
-  std::vector<size_t> item_bytes((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const mpe_image_format& f = used[(size_t)item_dense[(size_t)i]];
-    item_bytes[(size_t)i] =
-        (size_t)(f.rows - 1) * f.stride_bytes + (size_t)f.cols * (size_t)encoding_bytes_per_pixel(f.encoding);
-  }
-  if ((rc = check_device_images(h, items, n, 0, item_bytes.data())) != MPE_OK) return rc;
-  return submit_slots(h, items, item_setup, n, g, 0, prep.data(), n_setups, kFormatDeviceFrames, 0, MPE_ENC_MONO8, 0, false,
-                      &fm);
+  // (one distinct format: the gather and the records of that format's own entry)
+  const SlotPixels px = {frames_on_device != 0, item_dense.data(), used.data(), (int)used.size()};
+  return submit_tracked(h, items, item_setup, n, setups, n_setups, px, false);
 }
 
 int mpe_track_step_batch_formats(mpe_handle* h, const mpe_track_item* items, const int* item_setup, const int* item_format,
@@ -644,25 +594,15 @@ int mpe_track_step_batch_wide(mpe_handle* h, const mpe_track_item* items, const 
   if (!h || !items || n < 0 || !setups || n_setups < 1 || (!item_setup && n_setups != 1) || rows < 1 || cols < 1 ||
       !dets_out || !corr_out || !out)
     return fail(h, MPE_ERR_ARG, "bad argument");
-  const size_t bpp = (size_t)encoding_bytes_per_pixel(encoding);
-  if (!bpp) return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported (one of MPE_ENC_*)");
-  if (!frames_on_device && encoding_kind(encoding) != PIX_PLAIN)  // (what these codes answered before they existed)
-    return fail(h, MPE_ERR_UNSUPPORTED, "encoding not supported for host frames (Bayer and YUV: device frames)");
-  if (!frames_on_device && encoding != MPE_ENC_MONO8)
-    return fail(h, MPE_ERR_ARG, "host frames are mono8 (the encodings are decoded from device frames)");
-  if (stride_bytes < (size_t)cols * bpp) return fail(h, MPE_ERR_ARG, "bad argument");
+  const mpe_image_format f = {rows, cols, stride_bytes, encoding, src_big_endian};
+  // (this entry has always named the host rule before the stride: the three rules in its own order)
+  FormatRefusal no = refuse_encoding(encoding, frames_on_device != 0);
+  if (no.code == MPE_OK) no = refuse_host_encoding(encoding, frames_on_device != 0);
+  if (no.code == MPE_OK) no = refuse_size(f);
+  if (no.code != MPE_OK) return fail(h, no.code, no.msg);
   if (h->submit_seq != h->collect_seq) return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
-  FrameGeom g;
-  std::vector<TrackSetup> prep;
-  int rc = prepare_setups(h, items, item_setup, n, rows, cols, setups, n_setups, g, prep);
+  const int rc = submit_tracked(h, items, item_setup, n, setups, n_setups, SlotPixels{frames_on_device != 0, nullptr, &f, 1}, true);
   if (rc != MPE_OK || n == 0) return rc;
-  ENTER(h);
-  const PixelSource source = !frames_on_device ? kHostFrames : encoding == MPE_ENC_MONO8 ? kDeviceFrames : kEncodedDeviceFrames;
-  const size_t img_bytes = (size_t)(rows - 1) * stride_bytes + (size_t)cols * bpp;
-  if (frames_on_device && (rc = check_device_images(h, items, n, img_bytes)) != MPE_OK) return rc;
-  if ((rc = submit_slots(h, items, item_setup, n, g, stride_bytes, prep.data(), n_setups, source, img_bytes, encoding,
-                         src_big_endian ? 1 : 0, true)) != MPE_OK)
-    return rc;
   return run_wide_slots(h, n, dets_out, corr_out, out);
 }
 

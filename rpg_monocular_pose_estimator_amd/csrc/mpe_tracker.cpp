@@ -1,8 +1,8 @@
 // mpe_tracker.cpp — the stateful PoseEstimator state machine (tracking path) on top of the HIP
 // stages.  Host side only: a few 4x4 / 6-vector operations per frame; all image and pose compute
-// runs in the kernels through the public C ABI.  One state machine (BatchCtx) serves one stream and
+// runs in the kernels.  One state machine (BatchCtx) serves one stream and
 // N streams in lock step alike: its device steps are the lock-step submissions
-// (mpe_track_step_batch_setups_submit / _collect: detection in the ROI with correspondences,
+// (submit_tracked, mpe_host.h / mpe_track_step_batch_collect: detection in the ROI with correspondences,
 // validation and refinement) and mpe_solve_bruteforce_batch (re-initialisation); with
 // mpe_tracker_set_wide_frames, frames of 65 .. MPE_WIDE_DETECTIONS detections repeat those two steps
 // through mpe_track_step_batch_wide and mpe_solve_bruteforce_batch_wide.
@@ -19,12 +19,8 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/mpe.h"
-#include "mpe_pixel.h"  // (encoding_bytes_per_pixel)
-
-namespace mpe_host {
-void set_error(mpe_handle* h, const char* what);  // the text of mpe_last_error (mpe_options.cpp)
-}
+#include "mpe_host.h"   // (SlotPixels, submit_tracked, set_error)
+#include "mpe_pixel.h"  // (check_image_format, same_image_format)
 
 namespace {
 
@@ -643,18 +639,12 @@ bool same_camera_markers_params(const mpe_tracker* a, const mpe_tracker* b) {
   return a->markers == b->markers && a->D == b->D && !std::memcmp(a->K, b->K, sizeof(a->K)) &&
          !std::memcmp(&a->p, &b->p, sizeof(mpe_params));
 }
-bool same_image_format(const mpe_image_format& a, const mpe_image_format& b) {
-  return a.rows == b.rows && a.cols == b.cols && a.stride_bytes == b.stride_bytes && a.encoding == b.encoding &&
-         (a.encoding != MPE_ENC_MONO16 || (a.src_big_endian != 0) == (b.src_big_endian != 0));
-}
 bool same_setup(const mpe_tracker* a, const mpe_tracker* b) { return a->h == b->h && same_camera_markers_params(a, b); }
 
 struct BatchCtx {
   mpe_tracker* const* ts = nullptr;
   int n = 0;
   const uint8_t* const* imgs = nullptr;
-  int rows = 0, cols = 0;
-  size_t stride = 0;
   mpe_handle* h = nullptr;
   std::vector<BatchLane> L;
   std::vector<int> pend;  // lanes of the submitted, not yet collected DETECT batch
@@ -668,18 +658,17 @@ struct BatchCtx {
   // different set-ups on one handle; otherwise every lane must have the first one's.
   bool mixed = false;
   bool frames_on_device = false;  // imgs are device pointers (the *_device entries): the device-frame submission
-  int encoding = MPE_ENC_MONO8;   // of device frames (the *_device_encoded entries): the gather decodes; stride in source bytes
-  int big_endian = 0;             // ... their mono16 values are big-endian
   std::vector<mpe_track_setup> setups;
   std::vector<int> lane_setup, item_setup;
-  // lanes that differ in image format (the *_formats entries): lane i's images are of lane_formats[i] — rows, cols,
-  // stride and encoding per lane; formats = the distinct ones, lane_format the index of every lane's among them
-  const mpe_image_format* lane_formats = nullptr;
+  // the lanes' image formats — rows, cols, stride in source bytes, encoding —, checked by the entry: formats = the
+  // distinct ones (a uniform entry has one), lane_format the index of every lane's among them; item_format that of
+  // the gathered items, one_format: they all share item_format[0]
   std::vector<mpe_image_format> formats;
   std::vector<int> lane_format, item_format;
+  bool one_format = true;
 
+  // lane i's images are of f[i]
   void set_formats(const mpe_image_format* f) {
-    lane_formats = f;
     formats.clear();
     lane_format.assign((size_t)n, 0);
     for (int i = 0; i < n; ++i) {
@@ -689,8 +678,7 @@ struct BatchCtx {
       lane_format[(size_t)i] = (int)k;
     }
   }
-  int rows_of(int i) const { return lane_formats ? lane_formats[i].rows : rows; }
-  int cols_of(int i) const { return lane_formats ? lane_formats[i].cols : cols; }
+  const mpe_image_format& format_of(int i) const { return formats[(size_t)lane_format[(size_t)i]]; }
 
   int validate(mpe_tracker* const* ts_, int n_, bool mixed_ = false) {
     ts = ts_;
@@ -723,13 +711,11 @@ struct BatchCtx {
   }
 
   // begin of frame: pose_estimator.cpp:62-72 / 98-103 (predictWithROI)
-  void begin(const uint8_t* const* imgs_, int rows_, int cols_, size_t stride_, const double* times) {
+  void begin(const uint8_t* const* imgs_, const double* times) {
     imgs = imgs_;
-    rows = rows_;
-    cols = cols_;
-    stride = stride_;
     for (int i = 0; i < n; ++i) {
       mpe_tracker* t = ts[i];
+      const mpe_image_format& f = format_of(i);
       L[(size_t)i] = BatchLane();
       t->pose_updated = false;
       t->used_bruteforce = false;
@@ -739,25 +725,25 @@ struct BatchCtx {
       t->t_predicted = times[i];
       if (t->it_since_initialized < 1) {
         t->roi[0] = t->roi[1] = 0;
-        t->roi[2] = cols_of(i);
-        t->roi[3] = rows_of(i);
+        t->roi[2] = f.cols;
+        t->roi[3] = f.rows;
         L[(size_t)i].tracking = false;
       } else {
         if (t->it_since_initialized >= 2)
           t->predicted = predict_pose(t->current, t->previous, t->t_current, t->t_previous, t->t_predicted);
         for (int k = 0; k < n_markers(t); ++k)
           project(t, t->predicted, &t->markers[3 * k], t->predicted_px[2 * k], t->predicted_px[2 * k + 1]);
-        determine_roi(t, rows_of(i), cols_of(i));
+        determine_roi(t, f.rows, f.cols);
         L[(size_t)i].tracking = true;
       }
       L[(size_t)i].op = OP_DETECT;
     }
   }
 
-  bool is_big(int i) const { return (long long)ts[i]->roi[2] * ts[i]->roi[3] * 4 > (long long)rows_of(i) * cols_of(i); }
+  bool is_big(int i) const {
+    return (long long)ts[i]->roi[2] * ts[i]->roi[3] * 4 > (long long)format_of(i).rows * format_of(i).cols;
+  }
 
-  // submit the DETECT lanes of one size class (two classes, so that a few whole-image retries do not inflate every
-  // ROI slot of the batch); returns the number of lanes submitted or < 0
   // the lanes at `op` (of size class `big`; < 0: both — of format `fmt`; < 0: all) as items of a lock-step submission;
   // pend = those lanes
   void gather_items(BatchOp op, int big, int fmt = -1) {
@@ -765,10 +751,12 @@ struct BatchCtx {
     item_setup.clear();
     item_format.clear();
     pend.clear();
+    one_format = true;
     for (int i = 0; i < n; ++i) {
       if (L[(size_t)i].op != op || (big >= 0 && (int)is_big(i) != big)) continue;
       if (fmt >= 0 && lane_format[(size_t)i] != fmt) continue;
-      if (lane_formats) item_format.push_back(lane_format[(size_t)i]);
+      item_format.push_back(lane_format[(size_t)i]);
+      one_format = one_format && item_format.back() == item_format[0];
       const mpe_tracker* t = ts[i];
       mpe_track_item it;
       it.img = imgs[i];
@@ -782,20 +770,17 @@ struct BatchCtx {
       pend.push_back(i);
     }
   }
+  // submit the DETECT lanes of one size class (two classes, so that a few whole-image retries do not inflate every
+  // ROI slot of the batch); returns the number of lanes submitted or < 0
   int submit_detect(int big) {
     gather_items(OP_DETECT, big);
     if (items.empty()) return 0;
-    // (MPE_ENC_MONO8: the encoded entry hands the call to mpe_track_step_batch_setups_device_submit)
-    const int rc = lane_formats
-                       ? mpe_track_step_batch_formats_submit(h, items.data(), item_setup.data(), item_format.data(),
-                                                             (int)items.size(), formats.data(), (int)formats.size(),
-                                                             frames_on_device ? 1 : 0, setups.data(), (int)setups.size())
-                   : frames_on_device
-                       ? mpe_track_step_batch_setups_device_encoded_submit(h, items.data(), item_setup.data(), (int)items.size(),
-                                                                           rows, cols, stride, encoding, big_endian,
-                                                                           setups.data(), (int)setups.size())
-                       : mpe_track_step_batch_setups_submit(h, items.data(), item_setup.data(), (int)items.size(), rows, cols,
-                                                            stride, setups.data(), (int)setups.size());
+    // items of one format (always so in a uniform group): that format alone, as its own entry would submit it — the
+    // gather of one format is the faster kernel; else the group's table and every item's index into it
+    const mpe_image_format* f = one_format ? &formats[(size_t)item_format[0]] : formats.data();
+    const SlotPixels px = {frames_on_device, one_format ? nullptr : item_format.data(), f, one_format ? 1 : (int)formats.size()};
+    const int rc = submit_tracked(h, items.data(), item_setup.data(), (int)items.size(), setups.data(), (int)setups.size(), px,
+                                  false);
     if (rc != MPE_OK) {
       pend.clear();
       return rc;
@@ -866,46 +851,39 @@ struct BatchCtx {
       }
     } else if (ln.num_loops < 2) {  // too few LEDs in the ROI: search the whole image once
       t->roi[0] = t->roi[1] = 0;
-      t->roi[2] = cols_of(i);
-      t->roi[3] = rows_of(i);
+      t->roi[2] = format_of(i).cols;
+      t->roi[3] = format_of(i).rows;
       ln.op = OP_DETECT;
     } else {
       ln.op = OP_DONE;
     }
   }
 
-  // all OP_DETECT_WIDE lanes through ONE mpe_track_step_batch_wide (synchronous), advanced as collect_detect advances
-  // the narrow ones; lanes that differ in image format: one call per distinct format among them
+  // the OP_DETECT_WIDE lanes through mpe_track_step_batch_wide (synchronous), one call per distinct format that has
+  // such lanes, advanced as collect_detect advances the narrow ones
   int detect_wide() {
-    if (!lane_formats) return detect_wide_format(-1);
-    for (size_t f = 0; f < formats.size(); ++f) {
-      const int rc = detect_wide_format((int)f);
-      if (rc != MPE_OK) return rc;
-    }
-    return MPE_OK;
-  }
-  int detect_wide_format(int fmt) {
-    gather_items(OP_DETECT_WIDE, -1, fmt);
-    if (items.empty()) return MPE_OK;
-    const int m = (int)items.size();
-    wdets.resize((size_t)m);
-    corr.resize((size_t)m * 2 * MPE_MAX_MARKERS);
-    res.resize((size_t)m);
-    const mpe_image_format one = {rows, cols, stride, encoding, big_endian};
-    const mpe_image_format& f = fmt >= 0 ? formats[(size_t)fmt] : one;
-    const int rc = mpe_track_step_batch_wide(h, items.data(), item_setup.data(), m, f.rows, f.cols, f.stride_bytes,
-                                             frames_on_device ? 1 : 0, f.encoding, f.src_big_endian, setups.data(),
-                                             (int)setups.size(), wdets.data(), corr.data(), res.data());
-    if (rc != MPE_OK) {
+    for (size_t fi = 0; fi < formats.size(); ++fi) {
+      gather_items(OP_DETECT_WIDE, -1, (int)fi);
+      if (items.empty()) continue;
+      const int m = (int)items.size();
+      wdets.resize((size_t)m);
+      corr.resize((size_t)m * 2 * MPE_MAX_MARKERS);
+      res.resize((size_t)m);
+      const mpe_image_format& f = formats[fi];
+      const int rc = mpe_track_step_batch_wide(h, items.data(), item_setup.data(), m, f.rows, f.cols, f.stride_bytes,
+                                               frames_on_device ? 1 : 0, f.encoding, f.src_big_endian, setups.data(),
+                                               (int)setups.size(), wdets.data(), corr.data(), res.data());
+      if (rc != MPE_OK) {
+        pend.clear();
+        return rc;
+      }
+      for (int k = 0; k < m; ++k) {
+        const mpe_detections_wide& d = wdets[(size_t)k];
+        advance(pend[(size_t)k], d.n, d.status, d.undist_xy, d.dist_xy, res[(size_t)k], &corr[(size_t)k * 2 * MPE_MAX_MARKERS],
+                true);
+      }
       pend.clear();
-      return rc;
     }
-    for (int k = 0; k < m; ++k) {
-      const mpe_detections_wide& d = wdets[(size_t)k];
-      advance(pend[(size_t)k], d.n, d.status, d.undist_xy, d.dist_xy, res[(size_t)k], &corr[(size_t)k * 2 * MPE_MAX_MARKERS],
-              true);
-    }
-    pend.clear();
     return MPE_OK;
   }
 
@@ -1131,26 +1109,31 @@ struct BatchCtx {
 
 mpe_tracker::~mpe_tracker() { delete solo; }
 
+// one value for each of n lanes: what the uniform entries hand to the per-lane bodies (n as the caller gave it)
+template <class T>
+static std::vector<T> per_lane(int n, const T& v) {
+  return std::vector<T>((size_t)std::max(n, 0), v);
+}
+
 extern "C" {
 
-// the encoding of device frames, before a tracker's state is touched (the submission would refuse it as well, but only
-// after begin() has advanced the prediction): the codes of mpe_track_step_batch_setups_device_encoded_submit
-static int check_encoding(mpe_handle* h, int encoding, int cols, size_t stride_bytes) {
-  const int bpp = mpe::encoding_bytes_per_pixel(encoding);
-  if (!bpp) {
-    mpe_host::set_error(h, "encoding not supported (one of MPE_ENC_*)");
-    return MPE_ERR_UNSUPPORTED;
-  }
-  if (encoding != MPE_ENC_MONO8 && (cols < 1 || stride_bytes < (size_t)cols * (size_t)bpp)) {
-    mpe_host::set_error(h, "bad argument");
-    return MPE_ERR_ARG;
+// the formats of n lanes on handle h, before a tracker's state is touched: the codes and texts of the submit entries
+static int refuse_formats(mpe_handle* h, const mpe_image_format* formats, int n, bool on_device) {
+  for (int i = 0; i < n; ++i) {
+    const FormatRefusal no = check_image_format(formats[i], on_device);
+    if (no.code == MPE_OK) continue;
+    set_error(h, no.msg);
+    return no.code;
   }
   return MPE_OK;
 }
 
-static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
-                          size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated, bool mixed,
-                          bool on_device = false, int encoding = MPE_ENC_MONO8, int big_endian = 0) {
+// one time step of n trackers in lock step; formats[i] is stream i's.  host_as_given: the uniform host entries, whose
+// frames are mono8 by signature and whose size was never checked (one that holds no pixels fails the submission's ROI
+// check, with that check's text)
+static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, const mpe_image_format* formats,
+                          const double* times, mpe_result* out, int* info, int* updated, bool mixed, bool on_device,
+                          bool host_as_given = false) {
   if (!ts || n < 0 || !imgs || !times) return MPE_ERR_ARG;
   if (n == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -1158,11 +1141,10 @@ static int estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* i
   BatchCtx c;
   int rc = c.validate(ts, n, mixed);
   if (rc != MPE_OK) return rc;
-  if ((rc = check_encoding(c.h, encoding, cols, stride_bytes)) != MPE_OK) return rc;
+  if (!host_as_given && (rc = refuse_formats(c.h, formats, n, on_device)) != MPE_OK) return rc;
   c.frames_on_device = on_device;
-  c.encoding = encoding;
-  c.big_endian = big_endian;
-  c.begin(imgs, rows, cols, stride_bytes, times);
+  c.set_formats(formats);
+  c.begin(imgs, times);
   if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
     c.cancel();  // (a submission may still be in flight: leave the handle usable)
     return rc;
@@ -1178,7 +1160,9 @@ int mpe_tracker_estimate(mpe_tracker* t, const uint8_t* img, int rows, int cols,
   BatchCtx& c = *t->solo;
   int rc = c.validate(&t, 1);
   if (rc != MPE_OK) return rc;
-  c.begin(&img, rows, cols, stride_bytes, &time);
+  const mpe_image_format f = {rows, cols, stride_bytes, MPE_ENC_MONO8, 0};
+  c.set_formats(&f);
+  c.begin(&img, &time);
   if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
     c.cancel();
     return rc;
@@ -1192,88 +1176,49 @@ int mpe_tracker_estimate(mpe_tracker* t, const uint8_t* img, int rows, int cols,
 
 int mpe_tracker_estimate_batch(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
                                size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated) {
-  return estimate_batch(ts, n, imgs, rows, cols, stride_bytes, times, out, info, updated, false);
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, MPE_ENC_MONO8, 0});
+  return estimate_batch(ts, n, imgs, f.data(), times, out, info, updated, false, false, true);
 }
 
 int mpe_tracker_estimate_batch_mixed(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int rows, int cols,
                                      size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated) {
-  return estimate_batch(ts, n, imgs, rows, cols, stride_bytes, times, out, info, updated, true);
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, MPE_ENC_MONO8, 0});
+  return estimate_batch(ts, n, imgs, f.data(), times, out, info, updated, true, false, true);
 }
 
 // the frames in device memory (host array of device pointers); set-ups may be mixed, as in the entry above
 int mpe_tracker_estimate_batch_device(mpe_tracker* const* ts, int n, const uint8_t* const* d_imgs, int rows, int cols,
                                       size_t stride_bytes, const double* times, mpe_result* out, int* info, int* updated) {
-  return estimate_batch(ts, n, d_imgs, rows, cols, stride_bytes, times, out, info, updated, true, true);
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, MPE_ENC_MONO8, 0});
+  return estimate_batch(ts, n, d_imgs, f.data(), times, out, info, updated, true, true);
 }
 
 // the frames in device memory in the camera's own encoding: the ROI gather decodes them (stride_bytes in source bytes)
 int mpe_tracker_estimate_batch_device_encoded(mpe_tracker* const* ts, int n, const uint8_t* const* d_imgs, int rows, int cols,
                                               size_t stride_bytes, int encoding, int src_big_endian, const double* times,
                                               mpe_result* out, int* info, int* updated) {
-  return estimate_batch(ts, n, d_imgs, rows, cols, stride_bytes, times, out, info, updated, true, true, encoding,
-                        src_big_endian ? 1 : 0);
-}
-
-// the formats of the *_formats entries, before a tracker's state is touched: the codes of
-// mpe_track_step_batch_formats_submit
-static int check_formats(mpe_handle* h, const mpe_image_format* formats, int n, bool on_device) {
-  for (int i = 0; i < n; ++i) {
-    const mpe_image_format& f = formats[i];
-    const int bpp = mpe::encoding_bytes_per_pixel(f.encoding);
-    if (!bpp) {
-      mpe_host::set_error(h, "encoding not supported (one of MPE_ENC_*)");
-      return MPE_ERR_UNSUPPORTED;
-    }
-    if (!on_device && mpe::encoding_kind(f.encoding) != mpe::PIX_PLAIN) {  // (what these codes answered before)
-      mpe_host::set_error(h, "encoding not supported for host frames (Bayer and YUV: device frames)");
-      return MPE_ERR_UNSUPPORTED;
-    }
-    if (f.rows < 1 || f.cols < 1 || f.stride_bytes < (size_t)f.cols * (size_t)bpp) {
-      mpe_host::set_error(h, "bad argument");
-      return MPE_ERR_ARG;
-    }
-    if (!on_device && f.encoding != MPE_ENC_MONO8) {
-      mpe_host::set_error(h, "host frames are mono8 (the encodings are decoded from device frames)");
-      return MPE_ERR_ARG;
-    }
-  }
-  return MPE_OK;
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, encoding, src_big_endian});
+  return estimate_batch(ts, n, d_imgs, f.data(), times, out, info, updated, true, true);
 }
 
 // trackers whose cameras differ in image format (size, stride, encoding): formats[i] is stream i's
 int mpe_tracker_estimate_batch_formats(mpe_tracker* const* ts, int n, const uint8_t* const* imgs, int frames_on_device,
                                        const mpe_image_format* formats, const double* times, mpe_result* out, int* info,
                                        int* updated) {
-  if (!ts || n < 0 || !imgs || !formats || !times) return MPE_ERR_ARG;
-  if (n == 0) return 0;
-  for (int i = 0; i < n; ++i)
-    if (!imgs[i]) return MPE_ERR_ARG;
-  BatchCtx c;
-  int rc = c.validate(ts, n, true);
-  if (rc != MPE_OK) return rc;
-  if ((rc = check_formats(c.h, formats, n, frames_on_device != 0)) != MPE_OK) return rc;
-  c.frames_on_device = frames_on_device != 0;
-  c.set_formats(formats);
-  c.begin(imgs, 0, 0, 0, times);
-  if ((rc = c.submit_first()) != MPE_OK || (rc = c.finish()) != MPE_OK) {
-    c.cancel();  // (a submission may still be in flight: leave the handle usable)
-    return rc;
-  }
-  return c.outputs(out, 1, info, 8, updated);
+  if (!formats) return MPE_ERR_ARG;
+  return estimate_batch(ts, n, imgs, formats, times, out, info, updated, true, frames_on_device != 0);
 }
 
 // The lock-step loops of N streams over recorded sequences.  Trackers that live on DIFFERENT handles form groups
 // (one group per handle, each with the same camera / marker / parameter set inside the group); the groups are
 // pipelined against each other: while the device works on step k of one group, the host collects, advances and
 // packs another — the host work of a time step (~3 us per stream) hides behind the device latency (~0.2 ms).
-// (mixed: each group may mix cameras, marker sets and parameters — mpe_tracker_run_sequences_batch_mixed_threads;
-//  formats: stream i's images are of formats[i] and its frames frame_strides[i] bytes apart —
-//  mpe_tracker_run_sequences_batch_formats_threads; rows .. frame_stride_bytes and the encoding are then not read)
-static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows, int cols,
-                               size_t stride_bytes, size_t frame_stride_bytes, const double* times, mpe_result* out,
-                               int* info, int n_threads, bool mixed, bool on_device = false, int encoding = MPE_ENC_MONO8,
-                               int big_endian = 0, const mpe_image_format* formats = nullptr,
-                               const size_t* frame_strides = nullptr) {
+// Stream i's images are of formats[i] and its frames frame_strides[i] bytes apart.
+// (mixed: each group may mix cameras, marker sets and parameters — mpe_tracker_run_sequences_batch_mixed_threads)
+static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames,
+                               const mpe_image_format* formats, const size_t* frame_strides, const double* times,
+                               mpe_result* out, int* info, int n_threads, bool mixed, bool on_device,
+                               bool host_as_given = false) {
   if (!ts || n < 0 || !frames || !times || n_frames < 0 || n_threads < 1) return MPE_ERR_ARG;
   if (n == 0 || n_frames == 0) return 0;
   for (int i = 0; i < n; ++i)
@@ -1303,18 +1248,14 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
     const int rc = ctx[g].validate(gts[g].data(), (int)gts[g].size(), mixed);
     if (rc != MPE_OK) return rc;
     ctx[g].frames_on_device = on_device;
-    ctx[g].encoding = encoding;
-    ctx[g].big_endian = big_endian;
   }
   for (size_t g = 0; g < G; ++g) {
-    if (formats)
-      for (int i : members[g]) gformats[g].push_back(formats[i]);
-    const int rc = formats ? check_formats(hs[g], gformats[g].data(), (int)gformats[g].size(), on_device)
-                           : check_encoding(hs[g], encoding, cols, stride_bytes);
+    for (int i : members[g]) gformats[g].push_back(formats[i]);
+    if (host_as_given) continue;  // (as in estimate_batch)
+    const int rc = refuse_formats(hs[g], gformats[g].data(), (int)gformats[g].size(), on_device);
     if (rc != MPE_OK) return rc;
   }
-  if (formats)
-    for (size_t g = 0; g < G; ++g) ctx[g].set_formats(gformats[g].data());
+  for (size_t g = 0; g < G; ++g) ctx[g].set_formats(gformats[g].data());
   // The groups gs[0..) on the calling thread, pipelined against each other: while the device works on step k of one
   // group, the host collects, advances and packs another.  Groups share nothing (own handle, own trackers, own rows
   // of out / info), so disjoint sets of groups can also run on different host threads.
@@ -1340,10 +1281,10 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
           if (rc != MPE_OK) return rc;
         }
         for (size_t k = 0; k < members[g].size(); ++k) {
-          gimgs[g][k] = frames[members[g][k]] + (size_t)f * (frame_strides ? frame_strides[members[g][k]] : frame_stride_bytes);
+          gimgs[g][k] = frames[members[g][k]] + (size_t)f * frame_strides[members[g][k]];
           gtimes[g][k] = times[f];
         }
-        ctx[g].begin(gimgs[g].data(), rows, cols, stride_bytes, gtimes[g].data());
+        ctx[g].begin(gimgs[g].data(), gtimes[g].data());
         const int rc = ctx[g].submit_first();
         if (rc != MPE_OK) return rc;
       }
@@ -1384,16 +1325,20 @@ static int run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* con
 int mpe_tracker_run_sequences_batch_threads(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames,
                                             int rows, int cols, size_t stride_bytes, size_t frame_stride_bytes,
                                             const double* times, mpe_result* out, int* info, int n_threads) {
-  return run_sequences_batch(ts, n, frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
-                             n_threads, false);
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, MPE_ENC_MONO8, 0});
+  const std::vector<size_t> fs = per_lane(n, frame_stride_bytes);
+  return run_sequences_batch(ts, n, frames, n_frames, f.data(), fs.data(), times, out, info, n_threads,
+                             false, false, true);
 }
 
 int mpe_tracker_run_sequences_batch_mixed_threads(mpe_tracker* const* ts, int n, const uint8_t* const* frames,
                                                   int n_frames, int rows, int cols, size_t stride_bytes,
                                                   size_t frame_stride_bytes, const double* times, mpe_result* out,
                                                   int* info, int n_threads) {
-  return run_sequences_batch(ts, n, frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
-                             n_threads, true);
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, MPE_ENC_MONO8, 0});
+  const std::vector<size_t> fs = per_lane(n, frame_stride_bytes);
+  return run_sequences_batch(ts, n, frames, n_frames, f.data(), fs.data(), times, out, info, n_threads,
+                             true, false, true);
 }
 
 // frames[i] = DEVICE pointer to stream i's sequence (host array of device pointers); groups as in the entry above
@@ -1401,8 +1346,10 @@ int mpe_tracker_run_sequences_batch_device_threads(mpe_tracker* const* ts, int n
                                                    int n_frames, int rows, int cols, size_t stride_bytes,
                                                    size_t frame_stride_bytes, const double* times, mpe_result* out,
                                                    int* info, int n_threads) {
-  return run_sequences_batch(ts, n, d_frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
-                             n_threads, true, true);
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, MPE_ENC_MONO8, 0});
+  const std::vector<size_t> fs = per_lane(n, frame_stride_bytes);
+  return run_sequences_batch(ts, n, d_frames, n_frames, f.data(), fs.data(), times, out, info, n_threads,
+                             true, true);
 }
 
 // ... in the camera's own encoding (stride_bytes and frame_stride_bytes in source bytes)
@@ -1410,8 +1357,10 @@ int mpe_tracker_run_sequences_batch_device_encoded_threads(mpe_tracker* const* t
                                                            int n_frames, int rows, int cols, size_t stride_bytes,
                                                            size_t frame_stride_bytes, int encoding, int src_big_endian,
                                                            const double* times, mpe_result* out, int* info, int n_threads) {
-  return run_sequences_batch(ts, n, d_frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info,
-                             n_threads, true, true, encoding, src_big_endian ? 1 : 0);
+  const std::vector<mpe_image_format> f = per_lane(n, mpe_image_format{rows, cols, stride_bytes, encoding, src_big_endian});
+  const std::vector<size_t> fs = per_lane(n, frame_stride_bytes);
+  return run_sequences_batch(ts, n, d_frames, n_frames, f.data(), fs.data(), times, out, info, n_threads,
+                             true, true);
 }
 
 // ... every stream in an image format of its own
@@ -1420,8 +1369,8 @@ int mpe_tracker_run_sequences_batch_formats_threads(mpe_tracker* const* ts, int 
                                                     const size_t* frame_stride_bytes, const double* times, mpe_result* out,
                                                     int* info, int n_threads) {
   if (!formats || !frame_stride_bytes) return MPE_ERR_ARG;
-  return run_sequences_batch(ts, n, frames, n_frames, 0, 0, 0, 0, times, out, info, n_threads, true, frames_on_device != 0,
-                             MPE_ENC_MONO8, 0, formats, frame_stride_bytes);
+  return run_sequences_batch(ts, n, frames, n_frames, formats, frame_stride_bytes, times, out, info, n_threads, true,
+                             frames_on_device != 0);
 }
 
 int mpe_tracker_run_sequences_batch(mpe_tracker* const* ts, int n, const uint8_t* const* frames, int n_frames, int rows,
@@ -1437,8 +1386,8 @@ int mpe_tracker_run_sequence(mpe_tracker* t, const uint8_t* frames, int n_frames
                              size_t stride_bytes, size_t frame_stride_bytes, const double* times, mpe_result* out,
                              int* info) {
   if (!t || !frames || !times || n_frames < 0) return MPE_ERR_ARG;
-  return run_sequences_batch(&t, 1, &frames, n_frames, rows, cols, stride_bytes, frame_stride_bytes, times, out, info, 1,
-                             false);
+  const mpe_image_format f = {rows, cols, stride_bytes, MPE_ENC_MONO8, 0};
+  return run_sequences_batch(&t, 1, &frames, n_frames, &f, &frame_stride_bytes, times, out, info, 1, false, false, true);
 }
 
 }  // extern "C"

@@ -450,6 +450,7 @@ def test_usage_errors_leave_the_handle_usable(hip, scenes):
     assert call(rows=roi[1] + roi[3] - 1) == -1             # ROI outside the image
     assert call(enc=17) == -3                               # no such encoding
     assert call(enc=1) == -1                                # host frames are mono8
+    assert "host frames are mono8" in lib.mpe_last_error(hip._h).decode()   # (named before the stride, short for bgr8)
     assert call(dev=1) == -1                                # a host pointer is no device frame
     assert call(dev=1, enc=1, stride=cols) == -1            # stride below cols * bytes per pixel
     assert call(n=0) == 0
