@@ -981,6 +981,60 @@ int mpe_rig_calibrate(mpe_handle* h, const mpe_rig_camera* cameras, int n_camera
 int mpe_rig_calibration_start(const double* camera_pose, const int* updated, int n_views, int n_cameras,
                               int reference_camera, double* T_cam_rig_out, double* T_view_out, int* camera_linked);
 
+/* ---- calibrating the LED positions of a body from the sequences it was tracked in (a bundle adjustment on the device) ----
+ * Every other entry takes markers_xyz as exact; here they are the unknowns.  A recorded sequence of ONE body in front of
+ * 1 .. MPE_RIG_MAX_CAMERAS cameras: cameras bring K and the extrinsic E_c (camera <- rig), which is trusted and stays
+ * fixed (a single camera passes the identity).  View f holds the rows [view_begin[f], view_begin[f+1]) of row_camera /
+ * row_marker / row_uv (x 2, undistorted pixels), in any order, at most 256 of them; row_marker is an INDEX into
+ * markers_xyz (n_markers x 3, 1 .. MPE_MAX_MARKERS: the START positions).  T_view_init: n_views x 16 start poses, rig <-
+ * marker frame.  The unknowns are a left twist on the pose T_f of every used view and an additive delta_m on every FREE
+ * marker; the residual is mpe_rig_optimise_pose_batch's, e = uv - project(K_c, E_c T_f p_m).  Plain Gauss-Newton with a
+ * Schur complement over the view poses, unpivoted LDL^T, every sum in row / view / marker order by one lane (no atomics:
+ * the same bits from run to run); stop when the largest |component| of all twists and deltas of an iteration is <=
+ * step_tolerance, or after max_iterations.
+ * Which rows take part — a fixed point that starts with every marker free: a view is used when its rows on free markers
+ * number >= 4 and name >= 3 distinct free markers; a marker is free when it has >= 2 rows in used views.  A marker that
+ * is not free is HELD: its position comes back as given, bit for bit, its rows are dropped; the poses of unused views
+ * come back as given.  Fewer than 3 free markers or no used view: nothing is calibrated.  Rank deficiency beyond these
+ * rules (too few views, collinear free markers, no motion) is the caller's concern, as for optimisePose.
+ * The gauge: the body frame is arbitrary (6 degrees of freedom), and when no used view has used rows of two cameras the
+ * size is unobservable too (a seventh).  They are fixed by inner constraints: with c the centroid of the free markers'
+ * current positions and d_m = p_m - c, every step delta satisfies sum delta_m = 0, sum d_m x delta_m = 0 and, when scale
+ * is held, sum d_m . delta_m = 0 — the result is the shape the data give, placed (and, with scale held, sized) where the
+ * start values were, to first order.  scale: -1 held exactly when no used view has used rows of two cameras, 0 free, 1
+ * held; report.scale_held says which.
+ * markers_out: n_markers x 3; T_view_out (optional): n_views x 16; cov_out (optional): n_markers x 9, the 3 x 3 diagonal
+ * block of the pseudo-inverse of the reduced system of the last iteration — the inner-constraint covariance of the
+ * marker for unit pixel noise, zero for a held marker (scale = 1 on a rig that observes the size: the covariance of
+ * the estimate under that constraint, and every step is the constrained one); view_used (optional): n_views flags; report: status, iterations,
+ * views / rows used, markers_free, scale_held, rms = sqrt(mean e^2) over the used rows at the start and the final
+ * values, last_step, marker_state (1 calibrated, 2 held) and marker_rows (rows used) per marker.
+ * Returns 1 calibrated; 0 not (the rules above, or a non-finite output: status MPE_FRAME_NO_POSE, markers and poses come
+ * back exactly as given, cov_out zero); before any device work MPE_ERR_ARG (a null pointer, n_cameras outside 1 .. 16,
+ * n_markers outside 1 .. 16, n_views < 0, a camera or marker index out of range, a negative or decreasing view_begin,
+ * scale outside -1 .. 1, max_iterations < 1, step_tolerance not positive, a submission of the handle that is not
+ * collected yet) or MPE_ERR_UNSUPPORTED (a view of more than 256 rows); nothing is written then.  options == NULL: the
+ * defaults.  The views' records are worked through in chunks under "rig_ba_record_kb", as mpe_rig_calibrate's.  set
+ * "rig_ba_profile" 1: get "body_ba_us_linearise" / "_reduce" / "_solve" / "_update" / "_finish" / "_covariance" (device
+ * time of the last call per step, microseconds) and "body_ba_launches".
+ * The acceptance rules and the gauge are this library's own: the reference has no such step. */
+typedef struct mpe_body_calibration_options {
+  int scale;             /* -1 */
+  int max_iterations;    /* 50 */
+  double step_tolerance; /* 1e-10 */
+} mpe_body_calibration_options;
+void mpe_body_calibration_default_options(mpe_body_calibration_options* o);
+typedef struct mpe_body_calibration_report {
+  int status, iterations, views_used, rows_used, markers_free, scale_held;
+  double rms_before, rms_after, last_step;
+  int marker_state[MPE_MAX_MARKERS], marker_rows[MPE_MAX_MARKERS];
+} mpe_body_calibration_report;
+int mpe_body_calibrate(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const double* markers_xyz,
+                       int n_markers, const int* view_begin, const int* row_camera, const int* row_marker,
+                       const double* row_uv, int n_views, const double* T_view_init,
+                       const mpe_body_calibration_options* options, double* markers_out, double* T_view_out,
+                       double* cov_out, int* view_used, mpe_body_calibration_report* report);
+
 /* Stage-level batch entry points (used by the parity tests at every stage boundary). */
 /* detection only (a1): dets is a HOST array of n_frames records */
 int mpe_detect_batch(mpe_handle* h, const uint8_t* frames, int n_frames, int rows, int cols,

@@ -14,7 +14,8 @@ from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYP
                       tracker_run_sequences_batch_mixed, PinnedFrames, tracker_estimate_batch_device,
                       tracker_run_sequences_batch_device, ImageFormat, tracker_estimate_batch_formats,
                       tracker_run_sequences_batch_formats, Rig, MpeRigCamera, RIG_MAX_CAMERAS,
-                      RigCalibrator, rig_calibration_start,
+                      RigCalibrator, rig_calibration_start, BodyCalibrator, pack_body_views,
+                      MpeBodyCalibrationOptions, MpeBodyCalibrationReport,
                       MpeRigCalibrationOptions, MpeRigCalibrationReport,
                       MpeRigTrackOptions, MpeRigTrackInfo, RIG_TRACK_INFO_DTYPE,
                       MpeRigInitOptions, MpeRigInitInfo, RIG_INIT_INFO_DTYPE)
@@ -29,6 +30,7 @@ __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE"
            "tracker_run_sequences_batch_mixed", "PinnedFrames", "tracker_estimate_batch_device",
            "tracker_run_sequences_batch_device", "ImageFormat", "tracker_estimate_batch_formats",
            "tracker_run_sequences_batch_formats", "Rig", "MpeRigCamera", "RIG_MAX_CAMERAS", "RigCalibrator",
-           "rig_calibration_start", "MpeRigCalibrationOptions",
+           "rig_calibration_start", "MpeRigCalibrationOptions", "BodyCalibrator", "pack_body_views",
+           "MpeBodyCalibrationOptions", "MpeBodyCalibrationReport",
            "MpeRigCalibrationReport", "MpeRigTrackOptions", "MpeRigTrackInfo", "RIG_TRACK_INFO_DTYPE",
            "MpeRigInitOptions", "MpeRigInitInfo", "RIG_INIT_INFO_DTYPE"]

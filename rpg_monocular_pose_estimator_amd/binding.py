@@ -100,6 +100,17 @@ class MpeRigCalibrationReport(C.Structure):  # mpe_rig_calibration_report
                 ("camera_state", C.c_int * RIG_MAX_CAMERAS), ("camera_rows", C.c_int * RIG_MAX_CAMERAS)]
 
 
+class MpeBodyCalibrationOptions(C.Structure):  # mpe_body_calibration_options
+    _fields_ = [("scale", C.c_int), ("max_iterations", C.c_int), ("step_tolerance", C.c_double)]
+
+
+class MpeBodyCalibrationReport(C.Structure):  # mpe_body_calibration_report
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("views_used", C.c_int), ("rows_used", C.c_int),
+                ("markers_free", C.c_int), ("scale_held", C.c_int),
+                ("rms_before", C.c_double), ("rms_after", C.c_double), ("last_step", C.c_double),
+                ("marker_state", C.c_int * MAX_MARKERS), ("marker_rows", C.c_int * MAX_MARKERS)]
+
+
 RESULT_DTYPE = np.dtype([("T", "f8", (16,)), ("cov", "f8", (36,)), ("status", "i4"), ("n_det", "i4"),
                          ("n_corr", "i4"), ("gn_iterations", "i4")])
 DETECTIONS_DTYPE = np.dtype([("n", "i4"), ("status", "i4"), ("undist_xy", "f8", (2 * MAX_DETECTIONS,)),
@@ -157,7 +168,7 @@ def source_fingerprint():
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
                                   "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
                                   "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig_track.h", "mpe_rig_init.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
-                                  "mpe_rig_ba_plan.h"):
+                                  "mpe_rig_ba_plan.h", "mpe_body_ba.h", "mpe_body_ba_dev.h", "mpe_body_ba_plan.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -321,6 +332,11 @@ def load_library():
     lib.mpe_rig_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, ip, ip, dp, dp, C.c_int, dp,
                                       C.POINTER(MpeRigCalibrationOptions), dp, dp, dp, ip, C.POINTER(MpeRigCalibrationReport)]
     lib.mpe_rig_calibration_start.argtypes = [dp, ip, C.c_int, C.c_int, C.c_int, dp, dp, ip]
+    # the LED positions of a body calibrated from the sequences it was tracked in
+    lib.mpe_body_calibration_default_options.argtypes = [C.POINTER(MpeBodyCalibrationOptions)]
+    lib.mpe_body_calibration_default_options.restype = None
+    lib.mpe_body_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, dp, C.c_int, ip, ip, ip, dp, C.c_int, dp,
+                                       C.POINTER(MpeBodyCalibrationOptions), dp, dp, dp, ip, C.POINTER(MpeBodyCalibrationReport)]
     lib.mpe_tracker_get_correspondences.argtypes = [C.c_void_p, up, C.c_int]
     lib.mpe_tracker_get_image_points.argtypes = [C.c_void_p, dp, C.c_int]
     _lib = lib
@@ -1131,6 +1147,33 @@ class Handle:
         return dict(T_cam_rig=E[:n_cam], T_views=T[:n], cov=cov[:n_cam], view_used=used[:n].astype(bool),
                     report=rig_calibration_report_dict(rep, n_cam), ok=rc == 1)
 
+    def body_calibrate(self, cameras, views, markers, T_views, scale=-1, max_iterations=50, step_tolerance=1e-10):
+        """mpe_body_calibrate: the LED positions of ONE body from a recorded sequence (a bundle adjustment on the device
+        over the free markers and one pose per view; the extrinsics are fixed).  cameras: a list of (K 3x3, T_cam_rig
+        4x4 camera <- rig; a single camera: the identity); views: a list of row lists, a row = (camera index, marker
+        INDEX, undistorted pixel uv), any order; markers: (n, 3) START positions; T_views: (n_views, 4, 4) start poses,
+        rig <- marker frame; scale: -1 auto, 0 free, 1 held.
+        -> dict(markers (n, 3), T_views (n_views, 4, 4), cov (n, 3, 3), view_used (n_views) bool, report dict, ok): ok
+        False (report status 1) hands every marker and pose back as given."""
+        cams, begin, cam, mk_idx, uv = pack_body_views(cameras, views)
+        n, n_cam = len(views), len(cameras)
+        mk = _f64(markers).reshape(-1, 3)
+        T0 = _f64(T_views).reshape(-1, 16)
+        assert len(T0) == n
+        opt = MpeBodyCalibrationOptions(int(scale), int(max_iterations), float(step_tolerance))
+        P = np.zeros((max(len(mk), 1), 3))
+        T = np.zeros((max(n, 1), 4, 4))
+        cov = np.zeros((max(len(mk), 1), 3, 3))
+        used = np.zeros(max(n, 1), np.int32)
+        rep = MpeBodyCalibrationReport()
+        ip = C.POINTER(C.c_int)
+        rc = self._lib.mpe_body_calibrate(self._h, cams, n_cam, _dp(mk), len(mk), begin.ctypes.data_as(ip),
+                                          cam.ctypes.data_as(ip), mk_idx.ctypes.data_as(ip), _dp(uv), n, _dp(T0),
+                                          C.byref(opt), _dp(P), _dp(T), _dp(cov), used.ctypes.data_as(ip), C.byref(rep))
+        self._check(min(rc, 0), "mpe_body_calibrate")
+        return dict(markers=P[:len(mk)], T_views=T[:n], cov=cov[:len(mk)], view_used=used[:n].astype(bool),
+                    report=body_calibration_report_dict(rep, len(mk)), ok=rc == 1)
+
     # ---- one tracked frame: findLeds(ROI) + findCorrespondences + checkCorrespondences + optimisePose ----
     def track_step(self, img, roi, params, K, D, markers, predicted_px):
         img = np.ascontiguousarray(img, np.uint8)
@@ -1439,6 +1482,12 @@ class Tracker:
         handle._check(self._lib.mpe_tracker_set_camera(self._t, _dp(K), _dp(D), len(D)), "mpe_tracker_set_camera")
         self.set_params(params)
 
+    def set_markers(self, markers):
+        """setMarkerPositions(): another marker set (what BodyCalibrator.apply hands over)."""
+        markers = _f64(markers).reshape(-1, 3)
+        self._handle._check(self._lib.mpe_tracker_set_markers(self._t, _dp(markers), len(markers)), "mpe_tracker_set_markers")
+        self.markers = markers.copy()
+
     def set_params(self, params):
         self._handle._check(self._lib.mpe_tracker_set_params(self._t, C.byref(params)), "mpe_tracker_set_params")
 
@@ -1672,6 +1721,29 @@ def rig_calibration_report_dict(rep, n_cam):
                 camera_state=list(rep.camera_state[:n_cam]), camera_rows=list(rep.camera_rows[:n_cam]))
 
 
+def pack_body_views(cameras, views):
+    """The arrays mpe_body_calibrate takes: cameras [(K, T_cam_rig)], views = row lists of (camera, marker index, pixel
+    uv) -> (mpe_rig_camera array, view_begin, row_camera, row_marker, row_uv)."""
+    cams = (MpeRigCamera * max(1, len(cameras)))()
+    for c, (K, E) in zip(cams, cameras):
+        c.K[:] = _f64(K).reshape(9)
+        c.T_cam_rig[:] = _f64(E).reshape(16)
+    begin = np.zeros(len(views) + 1, np.int32)
+    begin[1:] = np.cumsum([len(rows) for rows in views])
+    flat = [r for rows in views for r in rows]
+    cam = np.ascontiguousarray([r[0] for r in flat], np.int32).reshape(-1)
+    mk = np.ascontiguousarray([r[1] for r in flat], np.int32).reshape(-1)
+    uv = _f64([r[2] for r in flat]).reshape(-1, 2)
+    return cams, begin, cam, mk, uv
+
+
+def body_calibration_report_dict(rep, n_markers):
+    return dict(status=rep.status, iterations=rep.iterations, views_used=rep.views_used, rows_used=rep.rows_used,
+                markers_free=rep.markers_free, scale_held=rep.scale_held,
+                rms_before=rep.rms_before, rms_after=rep.rms_after, last_step=rep.last_step,
+                marker_state=list(rep.marker_state[:n_markers]), marker_rows=list(rep.marker_rows[:n_markers]))
+
+
 def rig_calibration_start(camera_pose, updated, reference_camera=0):
     """mpe_rig_calibration_start (host only): start values for Handle.rig_calibrate from per-camera poses.  camera_pose:
     (n_views, n_cam, 4, 4), camera <- marker frame; updated: (n_views, n_cam).  -> (T_cam_rig (n_cam, 4, 4), T_views
@@ -1741,3 +1813,71 @@ class RigCalibrator:
         if self.result is None or not self.result["ok"]:
             raise MpeError("RigCalibrator.rig: no calibration (call solve() first; it must succeed)")
         return Rig(self.handle, self.trackers, self.result["T_cam_rig"])
+
+
+class BodyCalibrator:
+    """Calibrates the LED positions of a body from the sequences it is tracked in: step() drives the lock-step entry of
+    the trackers (one per camera, one handle, one marker set) as RigCalibrator.step does and keeps, for every tracker
+    that updated, its pose and its rows as (camera, marker index, undistorted pixel) — correspondences() over
+    image_points(); solve() starts from T_f = E_c^-1 P_c of the lowest camera that updated in view f and the trackers'
+    markers, and runs Handle.body_calibrate over the stored rows; apply() sets the calibrated markers on every tracker.
+    T_cam_rig: (N, 4, 4) extrinsics, camera <- rig; one tracker without extrinsics is the single-camera case (the
+    identity)."""
+
+    def __init__(self, handle, trackers, T_cam_rig=None):
+        self.handle = handle
+        self.trackers = list(trackers)
+        if T_cam_rig is None:
+            if len(self.trackers) != 1:
+                raise MpeError("BodyCalibrator: %d trackers need their extrinsics (T_cam_rig)" % len(self.trackers))
+            T_cam_rig = np.eye(4)[None]
+        self.T_cam_rig = _f64(T_cam_rig).reshape(-1, 4, 4).copy()
+        if len(self.T_cam_rig) != len(self.trackers):
+            raise MpeError("BodyCalibrator: one extrinsic per tracker")
+        self.views, self.poses, self.updated = [], [], []
+        self.result = None
+
+    def step(self, imgs, times, formats=None):
+        """One time step -> (records (N), info (N, 8), updated (N)): the lock-step entry's, unchanged."""
+        same = formats is None and not _is_torch(imgs[0]) and len({(np.shape(im), np.asarray(im).strides[0]) for im in imgs}) == 1
+        if same:
+            rec, info, upd = tracker_estimate_batch_mixed(self.trackers, imgs, times)
+        else:
+            rec, info, upd = tracker_estimate_batch_formats(self.trackers, imgs, times, formats)
+        rows = []
+        for c, t in enumerate(self.trackers):
+            if not upd[c]:
+                continue
+            xy = t.image_points()
+            rows += [(c, int(m) - 1, xy[j - 1].copy()) for m, j in t.correspondences()]
+        self.views.append(rows)
+        self.poses.append(rec["T"].reshape(len(self.trackers), 4, 4).copy())
+        self.updated.append(np.asarray(upd, bool).copy())
+        return rec, info, upd
+
+    def start(self):
+        """-> T_views (n, 4, 4): E_c^-1 P_c of the lowest camera that updated in the view, the identity if none did."""
+        T = np.tile(np.eye(4), (len(self.views), 1, 1))
+        for f, (P, upd) in enumerate(zip(self.poses, self.updated)):
+            for c in range(len(self.trackers)):
+                if upd[c]:
+                    T[f] = np.linalg.inv(self.T_cam_rig[c]) @ P[c]
+                    break
+        return T
+
+    def solve(self, scale=-1, max_iterations=50, step_tolerance=1e-10):
+        """-> Handle.body_calibrate's dict (kept as self.result), with the start values as "start"."""
+        T0 = self.start()
+        markers = self.trackers[0].markers.copy()
+        cameras = [(t.K, self.T_cam_rig[c]) for c, t in enumerate(self.trackers)]
+        out = self.handle.body_calibrate(cameras, self.views, markers, T0, scale, max_iterations, step_tolerance)
+        out["start"] = dict(markers=markers, T_views=T0)
+        self.result = out
+        return out
+
+    def apply(self):
+        """The calibrated markers onto every tracker (mpe_tracker_set_markers)."""
+        if self.result is None or not self.result["ok"]:
+            raise MpeError("BodyCalibrator.apply: no calibration (call solve() first; it must succeed)")
+        for t in self.trackers:
+            t.set_markers(self.result["markers"])

@@ -133,6 +133,9 @@ struct mpe_handle {
   int rig_ba_profile = 0;
   double rig_ba_ms[6] = {0, 0, 0, 0, 0, 0};
   int rig_ba_launches = 0;
+  // the same of the last mpe_body_calibrate call (under the same switch): get "body_ba_us_*", "body_ba_launches"
+  double body_ba_ms[6] = {0, 0, 0, 0, 0, 0};
+  int body_ba_launches = 0;
   // option "rig_launch_profile" = 1: mpe_rig_optimise_pose_batch and mpe_rig_track_batch bracket their ONE launch (and
   // mpe_rig_init_batch its four) with a
   // pair of events and leave its device time here (get "rig_launch_ns"); the copies are outside the pair

@@ -241,6 +241,10 @@ hipError_t launch_k_rig_init(const RigInitDev& d, hipStream_t s);
 #include "mpe_rig_ba_dev.h"
 enum { MPE_RIG_BA_LINEARISE = 0, MPE_RIG_BA_REDUCE, MPE_RIG_BA_SOLVE, MPE_RIG_BA_UPDATE, MPE_RIG_BA_FINISH, MPE_RIG_BA_COVARIANCE };
 hipError_t launch_k_rig_ba(int step, const RigBaDev& d, int first, int count, int flag, hipStream_t s);
+// the steps of mpe_body_calibrate (mpe_body_ba.h), launched the same way (the step numbers are the ones above); finish
+// with flag = 1 when the markers take their step
+#include "mpe_body_ba_dev.h"
+hipError_t launch_k_body_ba(int step, const BodyBaDev& d, int first, int count, int flag, hipStream_t s);
 hipError_t launch_k2_vote_wide(const mpe_detections_wide* dets, const SolveParams& sp, const BruteBlock* blocks,
                                int n_blocks, uint32_t* hist, hipStream_t s);
 hipError_t launch_k3_peel_wide(const mpe_detections_wide* dets, const uint32_t* hist, int n_items, int n_markers,

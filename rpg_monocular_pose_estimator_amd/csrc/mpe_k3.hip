@@ -1594,6 +1594,76 @@ hipError_t launch_k_rig_ba(int step, const RigBaDev& d, int first, int count, in
   return hipGetLastError();
 }
 
+// The LED positions of a body calibrated from the sequences it was tracked in (mpe_body_calibrate): the steps of
+// mpe_body_ba.h, launched as the ones above.  Waves of 64: linearise one block per used view of the chunk, reduce one
+// block per 3 x 3 block (i <= j) of the free markers (at most 136), solve and finish one block, update one lane per
+// view, covariance one block per free marker.  The host has checked the row counts and the camera and marker indices
+// and sized the records (body_ba_plan).
+#include "mpe_body_ba.h"
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_body_ba_linearise(BodyBaDev d, int first, int count) {
+  __shared__ BodyBaLinLds s_lin;
+  if ((int)blockIdx.x >= count) return;  // (block-uniform)
+  body_ba_linearise(s_lin, d, first + (int)blockIdx.x, first);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_body_ba_reduce(BodyBaDev d, int first, int count, int restart) {
+  __shared__ BodyBaRedLds s_red;
+  int i = 0, p = (int)blockIdx.x;  // block p of the upper triangle, row by row
+  while (i < d.n_free && p >= d.n_free - i) {
+    p -= d.n_free - i;
+    ++i;
+  }
+  if (i >= d.n_free) return;
+  body_ba_reduce(s_red, d, i, i + p, first, count, restart);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_body_ba_solve(BodyBaDev d) {
+  __shared__ BodyBaSolveLds s_solve;
+  body_ba_solve(s_solve, d);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_body_ba_covariance(BodyBaDev d) {
+  __shared__ BodyBaSolveLds s_solve;
+  if ((int)blockIdx.x >= d.n_free) return;
+  body_ba_covariance(s_solve, d, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_body_ba_update(BodyBaDev d, int first, int count) {
+  const int v = (int)(blockIdx.x * MPE_RIG_LANES + threadIdx.x);
+  if (v < count) body_ba_update_view(d, first + v, first);
+}
+__global__ __launch_bounds__(MPE_RIG_LANES) void k_body_ba_finish(BodyBaDev d, int apply) {
+  __shared__ RigBaFinLds s_fin;
+  body_ba_finish(s_fin, d, apply);
+}
+hipError_t launch_k_body_ba(int step, const BodyBaDev& d, int first, int count, int flag, hipStream_t s) {
+  const dim3 wave(MPE_RIG_LANES);
+  if (d.n_free < 3 || d.n_free > MPE_MAX_MARKERS || d.n_cam < 1 || d.n_cam > MPE_RIG_MAX_CAMERAS || d.n_views < 1 ||
+      first < 0 || count < 0 || first + count > d.n_views)
+    return hipErrorInvalidValue;
+  switch (step) {
+    case MPE_RIG_BA_LINEARISE:
+      if (count) hipLaunchKernelGGL(k_body_ba_linearise, dim3((unsigned)count), wave, 0, s, d, first, count);
+      break;
+    case MPE_RIG_BA_REDUCE:
+      hipLaunchKernelGGL(k_body_ba_reduce, dim3((unsigned)(d.n_free * (d.n_free + 1) / 2)), wave, 0, s, d, first, count, flag);
+      break;
+    case MPE_RIG_BA_SOLVE:
+      hipLaunchKernelGGL(k_body_ba_solve, dim3(1), wave, 0, s, d);
+      break;
+    case MPE_RIG_BA_UPDATE:
+      if (count)
+        hipLaunchKernelGGL(k_body_ba_update, dim3((unsigned)((count + MPE_RIG_LANES - 1) / MPE_RIG_LANES)), wave, 0, s, d, first,
+                           count);
+      break;
+    case MPE_RIG_BA_FINISH:
+      hipLaunchKernelGGL(k_body_ba_finish, dim3(1), wave, 0, s, d, flag);
+      break;
+    case MPE_RIG_BA_COVARIANCE:
+      hipLaunchKernelGGL(k_body_ba_covariance, dim3((unsigned)d.n_free), wave, 0, s, d);
+      break;
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_k3_tail(const mpe_detections* dets, const uint32_t* hist, int n_frames, const SolveParams& sp,
                           mpe_result* results, uint32_t* corr_out, const uint32_t* corr_in, const double* nn_pred,
                           double nn_tol, void* mid_buf, hipStream_t s, int mode) {

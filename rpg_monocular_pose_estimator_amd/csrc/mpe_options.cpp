@@ -302,6 +302,14 @@ int mpe_get_option(mpe_handle* h, const char* name, int* value) {
     if (k == 6) return fail(h, MPE_ERR_ARG, "unknown option");
     *value = (int)(h->rig_ba_ms[k] * 1e3 + 0.5);
   }
+  else if (n == "body_ba_launches") *value = h->body_ba_launches;
+  else if (n.rfind("body_ba_us_", 0) == 0) {
+    static const char* const steps[6] = {"linearise", "reduce", "solve", "update", "finish", "covariance"};
+    int k = 0;
+    while (k < 6 && n.substr(11) != steps[k]) ++k;
+    if (k == 6) return fail(h, MPE_ERR_ARG, "unknown option");
+    *value = (int)(h->body_ba_ms[k] * 1e3 + 0.5);
+  }
   else if (n == "track_ns_pack") *value = (int)(h->track_ns[0] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_enqueue") *value = (int)(h->track_ns[1] / std::max(1LL, h->track_steps));
   else if (n == "track_ns_wait") *value = (int)(h->track_ns[2] / std::max(1LL, h->track_steps));

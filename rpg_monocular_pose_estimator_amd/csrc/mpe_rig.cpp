@@ -8,17 +8,25 @@
 // here through the public entry.  mpe_rig_calibrate — the extrinsics of a rig from a recorded sequence of the body: which
 // rows take part and the iteration are mpe_rig_ba_plan.h (shared with the CPU tier), the steps are the k_rig_ba_* kernels
 // (mpe_k3.hip; logic in mpe_rig_ba.h), one launch each on the handle's stream; the host reads two doubles per iteration.
-// mpe_rig_calibration_start — start values from per-camera poses, host only.
+// mpe_rig_calibration_start — start values from per-camera poses, host only.  mpe_body_calibrate — the LED positions of
+// the body from such a sequence, the extrinsics fixed: the same iteration over the k_body_ba_* kernels (logic in
+// mpe_body_ba.h), the row rules in mpe_body_ba_plan.h.
 #include "mpe_host.h"
 #include "mpe_rig_ba_plan.h"
+#include "mpe_body_ba_plan.h"
 
 namespace {
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// the steps of rig_ba_iterate as launches on the handle's stream
-struct RigBaLaunches {
+// the steps of rig_ba_iterate as launches on the handle's stream: Dev / Launch are the extrinsic calibration's (RigBaDev,
+// launch_k_rig_ba) or the marker calibration's (BodyBaDev, launch_k_body_ba); ms / launches: where the handle keeps the
+// profile of that entry
+template <class Dev, hipError_t (*Launch)(int, const Dev&, int, int, int, hipStream_t)>
+struct BaLaunches {
   mpe_handle* h;
-  RigBaDev d;
+  Dev d;
+  double* ms;
+  int* launches;
   double* host_out;  // pinned: where finish's two doubles land
   hipError_t err = hipSuccess;
   struct Timed {
@@ -34,25 +42,25 @@ struct RigBaLaunches {
       timed.push_back(t);
       if (err != hipSuccess || (err = hipEventRecord(t.a, h->stream)) != hipSuccess) return 1;
     }
-    err = launch_k_rig_ba(step, d, first, count, flag, h->stream);
+    err = Launch(step, d, first, count, flag, h->stream);
     if (prof && err == hipSuccess) err = hipEventRecord(t.b, h->stream);
     return err == hipSuccess ? 0 : 1;
   }
   // behind the last synchronisation of the call: the sums per step into the handle, the events given back
   void read_out() {
     if (!timed.empty()) {
-      for (double& v : h->rig_ba_ms) v = 0;
-      h->rig_ba_launches = (int)timed.size();
+      for (int k = 0; k < 6; ++k) ms[k] = 0;
+      *launches = (int)timed.size();
     }
     for (const Timed& t : timed) {
-      float ms = 0;
-      if (t.a && t.b && hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) h->rig_ba_ms[t.step] += ms;
+      float el = 0;
+      if (t.a && t.b && hipEventElapsedTime(&el, t.a, t.b) == hipSuccess) ms[t.step] += el;
       if (t.a) (void)hipEventDestroy(t.a);
       if (t.b) (void)hipEventDestroy(t.b);
     }
     timed.clear();
   }
-  ~RigBaLaunches() { read_out(); }
+  ~BaLaunches() { read_out(); }
   int linearise(int first, int count) { return run(MPE_RIG_BA_LINEARISE, first, count, 0); }
   int reduce(int first, int count, bool restart) { return run(MPE_RIG_BA_REDUCE, first, count, restart ? 1 : 0); }
   int solve() { return run(MPE_RIG_BA_SOLVE, 0, 0, 0); }
@@ -496,8 +504,9 @@ int mpe_rig_calibrate(mpe_handle* h, const mpe_rig_camera* cameras, int n_camera
   uint8_t* dv = static_cast<uint8_t*>(h->frames.p);
   HIP_TRY(h, hipMemcpyAsync(dv, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemsetAsync(dv + o_cov, 0, (size_t)nf * 36 * sizeof(double), h->stream));
-  RigBaLaunches B;
+  BaLaunches<RigBaDev, launch_k_rig_ba> B;
   B.h = h;
+  B.ms = h->rig_ba_ms, B.launches = &h->rig_ba_launches;
   B.host_out = reinterpret_cast<double*>(mb + o_out);
   RigBaDev& d = B.d;
   d.cams = reinterpret_cast<mpe_rig_camera*>(dv + o_cam);
@@ -530,6 +539,142 @@ int mpe_rig_calibrate(mpe_handle* h, const mpe_rig_camera* cameras, int n_camera
   const double* T_back = reinterpret_cast<const double*>(mb + o_T);
   const double* cov_back = reinterpret_cast<const double*>(mb + o_cov);
   return rig_ba_hand_out(P, o, cam_back, T_back, cov_back, T_cam_rig_out, T_view_out, cov_out, report);
+}
+
+void mpe_body_calibration_default_options(mpe_body_calibration_options* o) {
+  if (!o) return;
+  o->scale = -1;
+  o->max_iterations = 50;
+  o->step_tolerance = 1e-10;
+}
+
+int mpe_body_calibrate(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const double* markers_xyz,
+                       int n_markers, const int* view_begin, const int* row_camera, const int* row_marker,
+                       const double* row_uv, int n_views, const double* T_view_init,
+                       const mpe_body_calibration_options* options, double* markers_out, double* T_view_out,
+                       double* cov_out, int* view_used, mpe_body_calibration_report* report) {
+  if (!h || n_views < 0) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (!cameras) return fail(h, MPE_ERR_ARG, "cameras is null");
+  if (!markers_xyz) return fail(h, MPE_ERR_ARG, "markers_xyz is null");
+  if (!view_begin) return fail(h, MPE_ERR_ARG, "view_begin is null");
+  if (!markers_out) return fail(h, MPE_ERR_ARG, "markers_out is null");
+  if (!report) return fail(h, MPE_ERR_ARG, "report is null");
+  if (n_views > 0 && !T_view_init) return fail(h, MPE_ERR_ARG, "T_view_init is null");
+  if (n_cameras < 1 || n_cameras > MPE_RIG_MAX_CAMERAS) return fail(h, MPE_ERR_ARG, "n_cameras outside 1 .. MPE_RIG_MAX_CAMERAS");
+  if (n_markers < 1 || n_markers > MPE_MAX_MARKERS) return fail(h, MPE_ERR_ARG, "n_markers outside 1 .. MPE_MAX_MARKERS");
+  mpe_body_calibration_options opt;
+  mpe_body_calibration_default_options(&opt);
+  if (options) opt = *options;
+  if (opt.scale < -1 || opt.scale > 1) return fail(h, MPE_ERR_ARG, "scale outside -1 .. 1");
+  if (opt.max_iterations < 1) return fail(h, MPE_ERR_ARG, "max_iterations must be >= 1");
+  if (!(opt.step_tolerance > 0)) return fail(h, MPE_ERR_ARG, "step_tolerance must be positive");
+  if (view_begin[0] < 0) return fail(h, MPE_ERR_ARG, "view_begin is negative");
+  for (int f = 0; f < n_views; ++f)
+    if (view_begin[f + 1] < view_begin[f]) return fail(h, MPE_ERR_ARG, "view_begin decreases");
+  const int r0 = view_begin[0], r1 = view_begin[n_views];
+  if (r1 > r0 && (!row_camera || !row_marker || !row_uv)) return fail(h, MPE_ERR_ARG, "a row array is null");
+  for (int j = r0; j < r1; ++j) {
+    if (row_camera[j] < 0 || row_camera[j] >= n_cameras) return fail(h, MPE_ERR_ARG, "camera index outside the rig");
+    if (row_marker[j] < 0 || row_marker[j] >= n_markers) return fail(h, MPE_ERR_ARG, "marker index outside the marker set");
+  }
+  if (h->pending_track_n || h->submit_seq != h->collect_seq)
+    return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+  for (int f = 0; f < n_views; ++f)
+    if (view_begin[f + 1] - view_begin[f] > MPE_RIG_MAX_CAMERAS * MPE_MAX_MARKERS)
+      return fail(h, MPE_ERR_UNSUPPORTED, "more than MPE_RIG_MAX_CAMERAS * MPE_MAX_MARKERS rows in a view");
+
+  BodyBaPlan P;
+  body_ba_plan(n_markers, view_begin, row_camera, row_marker, row_uv, n_views, MPE_BODY_BA_HEAD, MPE_BODY_BA_SLOT, P);
+  const int held = body_ba_scale_held(P, opt.scale);
+  body_ba_give_back(P, held, markers_xyz, n_views, T_view_init, markers_out, T_view_out, cov_out, view_used, report);
+  if (P.views_used == 0 || P.n_free < 3) return 0;
+
+  ENTER(h);
+  const int nv = P.views_used, nr = P.rows_used, nf = P.n_free;
+  // one block of device memory: [cameras | free markers | view_begin | masks | record offsets | row cameras | row markers
+  // | pixels | marker positions | view poses] from the host, then what the steps keep among themselves
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += up256(bytes);
+    return o;
+  };
+  const size_t o_cam = take((size_t)n_cameras * sizeof(mpe_rig_camera)), o_free = take(16 * sizeof(int)),
+               o_beg = take((size_t)(nv + 1) * sizeof(int)), o_mask = take((size_t)nv * sizeof(unsigned)),
+               o_cum = take((size_t)(nv + 1) * sizeof(long long)), o_rc = take((size_t)nr * sizeof(int)),
+               o_rf = take((size_t)nr * sizeof(int)), o_uv = take((size_t)nr * 2 * sizeof(double)),
+               o_mk = take((size_t)n_markers * 3 * sizeof(double)), o_T = take((size_t)nv * 16 * sizeof(double));
+  const size_t in_bytes = off;
+  const size_t o_cov = take((size_t)nf * 9 * sizeof(double)), o_out = take(2 * sizeof(double));
+  const size_t back_end = off;  // [o_mk, in_bytes) and [o_cov, back_end) come back
+  const size_t o_sse = take((size_t)nv * sizeof(double)), o_step = take((size_t)nv * sizeof(double)),
+               o_S = take((size_t)(nf * (nf + 1) / 2) * 18 * sizeof(double)), o_r = take((size_t)nf * 6 * sizeof(double)),
+               o_L = take((size_t)MPE_BODY_BA_TRI * sizeof(double)), o_delta = take((size_t)MPE_BODY_BA_MAX_N * sizeof(double)),
+               o_gauge = take((size_t)MPE_BODY_BA_GAUGE * sizeof(double));
+  const size_t dev_bytes = off;
+  { const int rc = grow_mailbox(h, back_end); if (rc != MPE_OK) return rc; }
+  uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
+  std::memset(mb, 0, in_bytes);
+  std::memcpy(mb + o_cam, cameras, (size_t)n_cameras * sizeof(mpe_rig_camera));
+  std::memcpy(mb + o_free, P.free_marker, 16 * sizeof(int));
+  std::memcpy(mb + o_beg, P.view_begin.data(), (size_t)(nv + 1) * sizeof(int));
+  std::memcpy(mb + o_mask, P.view_mask.data(), (size_t)nv * sizeof(unsigned));
+  std::memcpy(mb + o_cum, P.view_cum.data(), (size_t)(nv + 1) * sizeof(long long));
+  std::memcpy(mb + o_rc, P.row_cam.data(), (size_t)nr * sizeof(int));
+  std::memcpy(mb + o_rf, P.row_free.data(), (size_t)nr * sizeof(int));
+  std::memcpy(mb + o_uv, P.row_uv.data(), (size_t)nr * 2 * sizeof(double));
+  std::memcpy(mb + o_mk, markers_xyz, (size_t)n_markers * 3 * sizeof(double));
+  for (int v = 0; v < nv; ++v)
+    std::memcpy(mb + o_T + (size_t)v * 16 * sizeof(double), T_view_init + 16 * (size_t)P.view_of[(size_t)v], 16 * sizeof(double));
+  // the records of one chunk of views
+  const long long cap_doubles = (long long)(h->rig_ba_record_kb > 0 ? h->rig_ba_record_kb : 65536) * 1024 / 8;
+  const std::vector<std::pair<int, int>> chunks = rig_ba_chunks(P, cap_doubles);
+  long long rec_doubles = 0;
+  for (const auto& c : chunks)
+    rec_doubles = std::max(rec_doubles, P.view_cum[(size_t)(c.first + c.second)] - P.view_cum[(size_t)c.first]);
+  HIP_TRY(h, h->frames.reserve(dev_bytes));
+  HIP_TRY(h, h->scratch.reserve((size_t)rec_doubles * sizeof(double)));
+  uint8_t* dv = static_cast<uint8_t*>(h->frames.p);
+  HIP_TRY(h, hipMemcpyAsync(dv, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemsetAsync(dv + o_cov, 0, (size_t)nf * 9 * sizeof(double), h->stream));
+  BaLaunches<BodyBaDev, launch_k_body_ba> B;
+  B.h = h;
+  B.ms = h->body_ba_ms, B.launches = &h->body_ba_launches;
+  B.host_out = reinterpret_cast<double*>(mb + o_out);
+  BodyBaDev& d = B.d;
+  d.cams = reinterpret_cast<const mpe_rig_camera*>(dv + o_cam);
+  d.free_marker = reinterpret_cast<const int*>(dv + o_free);
+  d.n_cam = n_cameras, d.n_free = nf, d.n_views = nv;
+  d.scale_held = held;
+  d.view_begin = reinterpret_cast<const int*>(dv + o_beg);
+  d.view_mask = reinterpret_cast<const unsigned*>(dv + o_mask);
+  d.view_cum = reinterpret_cast<const long long*>(dv + o_cum);
+  d.row_cam = reinterpret_cast<const int*>(dv + o_rc);
+  d.row_free = reinterpret_cast<const int*>(dv + o_rf);
+  d.row_uv = reinterpret_cast<const double*>(dv + o_uv);
+  d.markers = reinterpret_cast<double*>(dv + o_mk);
+  d.T_view = reinterpret_cast<double*>(dv + o_T);
+  d.rec = static_cast<double*>(h->scratch.p);
+  d.sse = reinterpret_cast<double*>(dv + o_sse);
+  d.step = reinterpret_cast<double*>(dv + o_step);
+  d.Sacc = reinterpret_cast<double*>(dv + o_S);
+  d.racc = reinterpret_cast<double*>(dv + o_r);
+  d.Lf = reinterpret_cast<double*>(dv + o_L);
+  d.delta = reinterpret_cast<double*>(dv + o_delta);
+  d.gauge = reinterpret_cast<double*>(dv + o_gauge);
+  d.cov = reinterpret_cast<double*>(dv + o_cov);
+  d.out = reinterpret_cast<double*>(dv + o_out);
+  RigBaOutcome o;
+  if (rig_ba_iterate(B, chunks, opt.max_iterations, opt.step_tolerance, o)) return fail(h, MPE_ERR_HIP, "mpe_body_calibrate", B.err);
+  HIP_TRY(h, hipMemcpyAsync(mb + o_mk, dv + o_mk, (size_t)n_markers * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(mb + o_T, dv + o_T, (size_t)nv * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(mb + o_cov, dv + o_cov, (size_t)nf * 9 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  B.read_out();
+  const double* mk_back = reinterpret_cast<const double*>(mb + o_mk);
+  const double* T_back = reinterpret_cast<const double*>(mb + o_T);
+  const double* cov_back = reinterpret_cast<const double*>(mb + o_cov);
+  return body_ba_hand_out(P, o, mk_back, T_back, cov_back, markers_out, T_view_out, cov_out, report);
 }
 
 int mpe_rig_calibration_start(const double* camera_pose, const int* updated, int n_views, int n_cameras,

@@ -97,8 +97,10 @@ __device__ __forceinline__ void rig_ba_untri(int t, int& r, int& c) {
   c = r + (t - base);
 }
 
-// 6 x 6 solve with the factors in G.L / G.D (ldl6_solve's order); rhs and x may be the same array with any stride
-__device__ __forceinline__ void rig_ba_solve6(const RigBaLinLds& G, const double* rhs, int rs, double* x, int xs) {
+// 6 x 6 solve with the factors in G.L / G.D (ldl6_solve's order); rhs and x may be the same array with any stride (Lds:
+// RigBaLinLds, or mpe_body_ba.h's)
+template <class Lds>
+__device__ __forceinline__ void rig_ba_solve6(const Lds& G, const double* rhs, int rs, double* x, int xs) {
   double yv[6], xv[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i) {

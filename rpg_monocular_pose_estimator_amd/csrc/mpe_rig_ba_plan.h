@@ -92,7 +92,8 @@ inline void rig_ba_plan(int n_cam, int ref, const int* view_begin, const int* ro
 }
 
 // the used views cut into chunks whose records hold at most cap_doubles (a view alone may pass it): [first, first + count)
-inline std::vector<std::pair<int, int>> rig_ba_chunks(const RigBaPlan& P, long long cap_doubles) {
+template <class Plan>  // (RigBaPlan, or mpe_body_ba_plan.h's)
+inline std::vector<std::pair<int, int>> rig_ba_chunks(const Plan& P, long long cap_doubles) {
   std::vector<std::pair<int, int>> out;
   int first = 0;
   for (int f = 0; f < P.views_used; ++f) {

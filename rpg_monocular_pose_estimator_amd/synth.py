@@ -241,17 +241,20 @@ def make_sequence(config, n, seed, dt=0.02, lin_speed=0.15, ang_speed=0.6, dropo
 
 
 def make_rig_sequence(config, n, seed, cameras, T_cam_rig, dropout=None, dt=0.02, lin_speed=0.15, ang_speed=0.6,
-                      max_tries=20000, visible=None):
+                      max_tries=20000, visible=None, true_markers=None):
     """One body seen by the cameras of a calibrated rig: ONE smooth trajectory in the rig frame (make_sequence's model:
     constant twist + small jitter, frame k at time k*dt), accepted only when EVERY camera keeps all LEDs in view under
     make_sequence's margins (80 px on the first frame, 20 px / 12 px apart / 0.5 m deep afterwards), and one rendered
     sequence per camera.  cameras: a list of (K, D) (5 plumb-bob coefficients) or (K, D, rows, cols) — a camera without
     a size has the config's; T_cam_rig: (N, 4, 4), camera <- rig; dropout: {camera index: frames rendered with only 2
     LEDs}; visible: {camera index: {frame: marker indices rendered}} — the stated LEDs and only those, in that camera's
-    frame (a body that is partly occluded for every camera; it overrides dropout there).  -> dict(frames [N arrays (n, rows_c, cols_c)], T_true (n, 4, 4) rig <- marker frame, T_true_cam (N, n, 4, 4),
+    frame (a body that is partly occluded for every camera; it overrides dropout there); true_markers: (n_markers, 3),
+    where the LEDs of the rendered body REALLY are (default: the config's) — the returned `markers` stay the config's, what
+    a tracker is given from a ruler or a drawing, and `markers_true` are these (for BodyCalibrator).  -> dict(frames [N arrays (n, rows_c, cols_c)], T_true (n, 4, 4) rig <- marker frame, T_true_cam (N, n, 4, 4),
     times, cameras [(K, D, rows, cols)], T_cam_rig, markers)."""
     cfg = CONFIGS[config] if isinstance(config, str) else config
-    M = np.asarray(cfg["markers"])
+    M_nominal = np.asarray(cfg["markers"])
+    M = M_nominal if true_markers is None else np.asarray(true_markers, np.float64).reshape(M_nominal.shape)
     E = np.asarray(T_cam_rig, np.float64).reshape(-1, 4, 4)
     cams = []
     for c in cameras:
@@ -312,7 +315,7 @@ def make_rig_sequence(config, n, seed, cameras, T_cam_rig, dropout=None, dt=0.02
         frames.append(fr)
         T_cam.append(np.array([Ec @ T for T in Ts]))
     return dict(frames=frames, T_true=np.array(Ts), T_true_cam=np.array(T_cam), times=np.arange(n) * dt, cameras=cams,
-                T_cam_rig=E, markers=M)
+                T_cam_rig=E, markers=M_nominal, markers_true=M)
 
 
 CLUTTER_KINDS = ("salt", "salt_dense", "patch", "ring", "grid", "d4", "d16")

@@ -55,4 +55,17 @@ g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-saniti
     -DRIG_BA_HOST_MAIN -I $RB -I tests/host/stub -I rpg_monocular_pose_estimator_amd/csrc tests/host/rig_ba_host.cpp \
     -o $RB/rig_ba_host && $RB/rig_ba_host || rc=1
 rm -rf "$RB"
+# the steps of the marker calibration, the k_body_ba_* kernels' logic (csrc/mpe_body_ba.h) behind mpe_rig_ba.h and the
+# same cut of mpe_k3.hip, driven by the library's own row rules (csrc/mpe_body_ba_plan.h) and iteration: a stand-alone
+# program too (exact-pixel bodies of 4 .. 16 markers back to their shape, again in chunks of one view bit for bit, the
+# row rules)
+BB=$(mktemp -d)
+python -c "
+import rpg_monocular_pose_estimator_amd as mpe
+hip = mpe.device_source(); i = hip.index('struct T34 {')
+open('$BB/k3_extract.inc', 'w').write(hip[i:hip.index('#define K3_GROUP', i)])" && \
+g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+    -DBODY_BA_HOST_MAIN -I $BB -I tests/host/stub -I rpg_monocular_pose_estimator_amd/csrc tests/host/body_ba_host.cpp \
+    -o $BB/body_ba_host && $BB/body_ba_host || rc=1
+rm -rf "$BB"
 exit $rc
