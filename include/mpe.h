@@ -319,8 +319,23 @@ int mpe_p3p_batch(mpe_handle* h, const double* feature_vectors, const double* wo
                   double* solutions, int* status);
 /* P3P::solveQuartic (p3p.h:127, p3p.cpp:238-286): factors n x 5 (highest power first), real_roots n x 4
  * (real parts of the four complex Ferrari roots, like the reference).  variant 0 = IEEE operators
- * (as the validation kernel uses it), 1 = the voting kernel's literal-order variant. */
+ * (as the validation kernel uses it), 1 = the voting kernel's literal-order variant,
+ * 2 = the three complex powers as libstdc++ / glibc evaluate them (solve_quartic_glibc, the function
+ * the strict voting item of "vote_arith" 3 / 4 calls).  Any other variant: MPE_ERR_ARG. */
 int mpe_solve_quartic_batch(mpe_handle* h, const double* factors, int n, int variant, double* real_roots);
+/* The stage-level parity entry of csrc/mpe_ddmath.h (the libstdc++ / glibc restatement behind "vote_arith"
+ * 3 / 4): primitive `which` at the n argument pairs (a[i], b[i]), out n x 2 = (out0, out1) per pair.
+ * Selectors (csrc/mpe_ddmath_eval.h; one argument: b is read and ignored, one result: out1 = 0):
+ * 0 log, 1 log1p (correctly rounded), 2 exp, 3 sin, 4 cos, 5 hypot_g(a, b), 6 atan2(y = a, x = b),
+ * 7 pow(a, b), 8 log1p_g; 9 clog_g(re = a, im = b); 10 / 11 / 12 cpow_g(re = a, im = b, y) at y = 1/3,
+ * 2, 3; 13 the quartic's complex square root; 14 x2y2m1_g(a, b); the unrounded double-double pairs
+ * (hi, lo) with x = the exact product a b and y = the exact sum a + b: 15 x, 16 x + y, 17 x y, 18 x / y,
+ * 19 sqrt x, 20 log x, 21 exp x, 22 atan x, 23 / 24 the sine / cosine of a before their one rounding.
+ * It exists for tests that hold the device build of that header to the bits of its host build; nothing
+ * on the estimation path calls it.  n == 0: MPE_OK; a selector outside 0 .. MPE_DDMATH_SELECTORS - 1,
+ * n < 0 or a null pointer with n > 0: MPE_ERR_ARG (the handle stays usable). */
+#define MPE_DDMATH_SELECTORS 25
+int mpe_ddmath_batch(mpe_handle* h, int which, const double* a, const double* b, int n, double* out);
 
 /* LEDDetector::determineROI (led_detector.h:105, led_detector.cpp:114-179): bounding box of the predicted
  * (undistorted) pixel positions, its two corners distorted, grown by border_size, clipped to the

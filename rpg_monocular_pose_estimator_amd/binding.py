@@ -164,7 +164,7 @@ def source_fingerprint():
     (profiles/round3_pmc.json) to the code a bench run times."""
     import hashlib
     hsh = hashlib.sha256()
-    for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
+    for name in DEVICE_SOURCES + ("mpe_k1b_dev.h", "mpe_ddmath.h", "mpe_ddmath_eval.h", "mpe_p3p.h", "mpe_internal.h", "mpe_host.h", "mpe_schedule.cpp",
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
                                   "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
                                   "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig_track.h", "mpe_rig_init.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
@@ -219,6 +219,7 @@ def load_library():
                                   C.POINTER(C.c_int)]
     lib.mpe_solve_bruteforce.argtypes = [C.c_void_p, dp, C.c_int, dp, C.c_int, dp, C.POINTER(MpeParams),
                                          C.POINTER(MpeResult), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.mpe_ddmath_batch.argtypes = [C.c_void_p, C.c_int, dp, dp, C.c_int, dp]
     ip, up = C.POINTER(C.c_int), C.POINTER(C.c_uint32)
     lib.mpe_solve_bruteforce_batch.argtypes = [C.c_void_p, dp, ip, C.c_int, dp, C.c_int, dp, C.POINTER(MpeParams),
                                                C.c_void_p, up, up]
@@ -1315,6 +1316,17 @@ class Handle:
         self._check(self._lib.mpe_solve_quartic_batch(self._h, _dp(f), len(f), int(variant), _dp(r)),
                     "mpe_solve_quartic_batch")
         return r
+
+    def ddmath_batch(self, which, a, b=None):
+        """Primitive `which` of csrc/mpe_ddmath.h (selectors: include/mpe.h) at the pairs (a[i], b[i]); b defaults to
+        a.  -> (n, 2) = (out0, out1)."""
+        a = _f64(a).reshape(-1)
+        b = a if b is None else _f64(b).reshape(-1)
+        if len(b) != len(a):
+            raise MpeError("a and b differ in length")
+        out = np.zeros((len(a), 2))
+        self._check(self._lib.mpe_ddmath_batch(self._h, int(which), _dp(a), _dp(b), len(a), _dp(out)), "mpe_ddmath_batch")
+        return out
 
     # ---- estimateBodyPose on a fresh estimator per frame -------------------------------------
     def estimate_batch(self, frames, markers, K, D, params):

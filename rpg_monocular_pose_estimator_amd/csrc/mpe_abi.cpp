@@ -334,7 +334,7 @@ int mpe_p3p_batch(mpe_handle* h, const double* feature_vectors, const double* wo
 }
 
 int mpe_solve_quartic_batch(mpe_handle* h, const double* factors, int n, int variant, double* real_roots) {
-  if (!h || n < 0 || (n > 0 && (!factors || !real_roots)) || (variant != 0 && variant != 1))
+  if (!h || n < 0 || (n > 0 && (!factors || !real_roots)) || variant < 0 || variant > 2)
     return fail(h, MPE_ERR_ARG, "bad argument");
   if (n == 0) return MPE_OK;
   ENTER(h);
@@ -345,6 +345,24 @@ int mpe_solve_quartic_batch(mpe_handle* h, const double* factors, int n, int var
   HIP_TRY(h, hipMemcpyAsync(d_f, factors, in, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, launch_quartic_batch(d_f, n, variant, d_r, h->stream));
   HIP_TRY(h, hipMemcpyAsync(real_roots, d_r, out, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPE_OK;
+}
+
+int mpe_ddmath_batch(mpe_handle* h, int which, const double* a, const double* b, int n, double* out) {
+  if (!h || n < 0 || (n > 0 && (!a || !b || !out)) || which < 0 || which >= MPE_DDMATH_SELECTORS)
+    return fail(h, MPE_ERR_ARG, "bad argument");
+  if (n == 0) return MPE_OK;
+  ENTER(h);
+  const size_t in = (size_t)n * sizeof(double);
+  HIP_TRY(h, h->scratch.reserve(4 * in + 64));
+  double* d_a = static_cast<double*>(h->scratch.p);
+  double* d_b = d_a + n;
+  double* d_o = d_b + n;
+  HIP_TRY(h, hipMemcpyAsync(d_a, a, in, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d_b, b, in, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, launch_ddmath_batch(which, d_a, d_b, n, d_o, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(out, d_o, 2 * in, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return MPE_OK;
 }

@@ -19,6 +19,10 @@
 //     evaluated in double-double (~2^-100) and rounded once.  glibc's own versions are within 0.51 - 0.55 ulp, so the
 //     two agree except where glibc itself misrounds (tests/test_ddmath_host.py measures the rate against this image's
 //     libm on millions of arguments: the CPU tier compiles this header for the host).
+// The device build is held to the bits of that host build primitive by primitive (mpe_ddmath_eval.h, k_ddmath_batch,
+// tests/test_ddmath_device.py).  That only works while nothing here calls the platform's math library on an argument a
+// caller can reach: the device's log / atan2 / sincos are not glibc's.  The calls left answer infinities, NaN, zeros and
+// arguments past the documented ranges.
 // Everything is __device__ code without tables in memory beyond a few constants; it runs for the 0.2 - 0.3 % of the
 // hypotheses the fast kernels hand to the strict arithmetic (option "vote_arith" = 3) and for the strict kernel.
 #pragma once
@@ -187,13 +191,11 @@ MPE_DDM double pow_cr(double x, double y) {
   return to_double(exp_dd(p));
 }
 // sin and cos of |theta| <= pi (the quartic only asks for |theta| <= pi / 3): theta / 16 by the Taylor series (12 terms:
-// (pi / 16)^24 / 24! < 2^-135), four angle doublings.  Relative accuracy ~2^-98 for the sine everywhere and for the
-// cosine away from pi / 2.
-MPE_DDM void sincos_cr(double theta, double& s_out, double& c_out) {
-  if (!(fabs(theta) <= 3.1415926535897936)) {
-    sincos(theta, &s_out, &c_out);
-    return;
-  }
+// (pi / 16)^24 / 24! < 2^-135), four angle doublings.  Relative accuracy ~2^-98 for the sine up to pi / 2 (near pi its
+// last doubling multiplies by a cosine that cancelled) and for the cosine away from pi / 2.  sincos_dd: the two
+// double-double values before their one rounding (|theta| <= pi); sincos_cr calls it for |theta| <= 1.1 and, behind a
+// reduction by quarter turns, for |theta| <= pi / 4.
+MPE_DDM void sincos_dd(double theta, dd& s_out, dd& c_out) {
   const dd a = {ldexp(theta, -4), 0.0};
   const dd a2 = mul(a, a);
   dd sa = fac_rec(23), ca = fac_rec(22);
@@ -210,6 +212,35 @@ MPE_DDM void sincos_cr(double theta, double& s_out, double& c_out) {
     c = neg(c);
     s = s2;
   }
+  s_out = s;
+  c_out = c;
+}
+MPE_DDM void sincos_cr(double theta, double& s_out, double& c_out) {
+  dd s, c;
+  if (fabs(theta) <= 1.1) {  // (what the quartic asks for, with a margin)
+    sincos_dd(theta, s, c);
+  } else if (fabs(theta) <= 3.0 * kPi[0]) {
+    // 1.1 < |theta| <= 3 pi_d (y arg z for y = 2, 3 and a general z).  Not the library's sincos — the device library's
+    // is not glibc's — but k = 1 .. 6 quarter turns taken off in double-double: k pi / 2 = K.hi + d with K = k (x) kPi2[0]
+    // exact and d = K.lo + k (kPi2[1] + kPi2[2]) ~ k 6e-17; r = |theta| - K.hi is exact (Sterbenz), |r| <= pi / 4, where
+    // sincos_dd is accurate in both, and sin(r - d) = sin r (1 - d^2 / 2) - cos r d, cos(r - d) = cos r (1 - d^2 / 2)
+    // + sin r d; the quadrant k mod 4 then says which of the two is which.
+    const double at = fabs(theta), k = rint(at * 0.6366197723675814);
+    const dd K = two_prod(k, kPi2[0]);
+    const dd d = add(mul(dd{kPi2[1], kPi2[2]}, k), K.lo);
+    dd sr, cr;
+    sincos_dd(at - K.hi, sr, cr);
+    const dd h = scale2(mul(d, d), -1);
+    const dd sq = sub(sub(sr, mul(cr, d)), mul(sr, h));
+    const dd cq = sub(add(cr, mul(sr, d)), mul(cr, h));
+    const int q = (int)k & 3;
+    s = q == 0 ? sq : q == 1 ? cq : q == 2 ? neg(sq) : neg(cq);
+    c = q == 0 ? cq : q == 1 ? neg(sq) : q == 2 ? neg(cq) : sq;
+    if (theta < 0.0) s = neg(s);
+  } else {
+    sincos(theta, &s_out, &c_out);  // (beyond three half turns, infinities, NaN: the library's answer)
+    return;
+  }
   s_out = to_double(s);
   c_out = to_double(c);
 }
@@ -225,11 +256,26 @@ MPE_DDM dd atan_dd(dd t) {
 }
 MPE_DDM double atan2_cr(double y, double x) {
   if (!(x == x) || !(y == y)) return x + y;
-  const double ay = fabs(y), ax = fabs(x);
+  double ay = fabs(y), ax = fabs(x);
   if (ay == 0.0) return __builtin_signbit(x) ? copysign(kPi[0], y) : y;  // atan2(+-0, -x) = +-pi, atan2(+-0, +x) = +-0
   if (ax == 0.0) return copysign(kPi2[0], y);
-  if (!(ax < INFINITY) || !(ay < INFINITY) || ax < 0x1p-500 || ay < 0x1p-500 || ax > 0x1p500 || ay > 0x1p500)
-    return atan2(y, x);  // (infinities, and magnitudes whose quotient leaves the normal range: the library's answer)
+  if (!(ax < INFINITY) || !(ay < INFINITY)) return atan2(y, x);  // (infinities: the library's multiples of pi / 4)
+  if (ax < 0x1p-500 || ay < 0x1p-500 || ax > 0x1p500 || ay > 0x1p500) {
+    // Magnitudes whose quotient or whose double-double parts could leave the normal range (subnormal operands of clog
+    // among them).  Not the library's atan2 — the device library's is not glibc's and not correctly rounded — but the
+    // same evaluation after an exact rescaling: both operands times one power of two, the larger one into
+    // [2^-500, 2^500]; where that leaves the smaller one more than 2^400 below the larger, atan t = t (1 - t^2 / 3 ..)
+    // rounds as t does and pi / 2 -+ t, pi - t as pi / 2 and pi.
+    const double big = ax > ay ? ax : ay;
+    const double k = big > 0x1p500 ? 0x1p-600 : big < 0x1p-500 ? 0x1p600 : 1.0;
+    const double sx = ax * k, sy = ay * k;
+    if ((sx < sy ? sx : sy) < (sx < sy ? sy : sx) * 0x1p-400) {
+      if (ay > ax) return copysign(kPi2[0], y);
+      return x < 0.0 ? copysign(kPi[0], y) : copysign(ay / ax, y);
+    }
+    ax = sx;  // (exact: the smaller one is within 2^400 of the larger, so it stayed normal)
+    ay = sy;
+  }
   const bool inv = ay > ax;
   const dd t = inv ? div(dd{ax, 0.0}, dd{ay, 0.0}) : div(dd{ay, 0.0}, dd{ax, 0.0});
   dd a = atan_dd(t);

@@ -259,5 +259,7 @@ hipError_t launch_to_mono8(const uint8_t* src, size_t src_stride, size_t src_fra
 hipError_t launch_spin(unsigned long long ticks_100mhz, hipStream_t s);
 hipError_t launch_p3p_batch(const double* fv, const double* wp, int n, double* sol, int* status, hipStream_t s);
 hipError_t launch_quartic_batch(const double* factors, int n, int variant, double* roots, hipStream_t s);
+// primitive `which` of mpe_ddmath.h (selectors: mpe_ddmath_eval.h) at n argument pairs, out = n x (out0, out1)
+hipError_t launch_ddmath_batch(int which, const double* a, const double* b, int n, double* out, hipStream_t s);
 
 }  // namespace mpe

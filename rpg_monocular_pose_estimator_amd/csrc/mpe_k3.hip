@@ -6,6 +6,7 @@
 #include "mpe_pixel.h"    // (gray_px, mono16_px: the per-pixel conversion of k_to_mono8, shared with the encoded ROI gather)
 #include "mpe_wide_peel.h"  // (k3_peel_wide's logic, shared with the CPU tier)
 #include "mpe_wide_nn.h"    // (k_nn_wide's, likewise)
+#include "mpe_ddmath_eval.h"  // (k_ddmath_batch's one function, likewise)
 namespace mpe {
 //@file-prologue-end
 // =============================================================================================
@@ -1743,9 +1744,25 @@ __global__ __launch_bounds__(64) void k_quartic_batch(const double* __restrict__
   double r[4];
   if (variant == 1)
     solve_quartic_lit2(a[0], a[1], a[2], a[3], a[4], r);  // the voting kernel's variant
+  else if (variant == 2)
+    solve_quartic_glibc(a[0], a[1], a[2], a[3], a[4], r);  // vote_arith 3 / 4: the out-of-line function the strict item calls
   else
     solve_quartic(a[0], a[1], a[2], a[3], a[4], r);  // IEEE operators (validation kernel)
   for (int k = 0; k < 4; ++k) roots[(size_t)i * 4 + k] = r[k];
+}
+
+// mpe_ddmath.h primitive by primitive (ddm::eval, mpe_ddmath_eval.h: the function the CPU tier's host scaffold calls):
+// one lane per argument pair, out = n x (out0, out1).  For the parity tests that hold this build of the header to the
+// bits of its host build; on no other path.
+static_assert(ddm::EV_COUNT == MPE_DDMATH_SELECTORS, "include/mpe.h documents the selectors of mpe_ddmath_eval.h");
+__global__ __launch_bounds__(64) void k_ddmath_batch(int which, const double* __restrict__ a, const double* __restrict__ b,
+                                                    int n, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double o0, o1;
+  ddm::eval(which, a[i], b[i], o0, o1);
+  out[(size_t)i * 2] = o0;
+  out[(size_t)i * 2 + 1] = o1;
 }
 
 // =============================================================================================
@@ -1918,6 +1935,12 @@ hipError_t launch_p3p_batch(const double* fv, const double* wp, int n, double* s
 hipError_t launch_quartic_batch(const double* factors, int n, int variant, double* roots, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_quartic_batch, dim3((n + 63) / 64), dim3(64), 0, s, factors, n, variant, roots);
+  return hipGetLastError();
+}
+
+hipError_t launch_ddmath_batch(int which, const double* a, const double* b, int n, double* out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ddmath_batch, dim3((n + 63) / 64), dim3(64), 0, s, which, a, b, n, out);
   return hipGetLastError();
 }
 

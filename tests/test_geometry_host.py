@@ -4,37 +4,18 @@ checked against the oracle with the same criteria the `-m gpu` tests apply to th
 but it can still run the source the GPU runs; only the hardware reciprocal / rsqrt seeds of the fast arithmetic are
 replaced (tests/host/stub/hip/hip_runtime.h).  Reference: p3p.cpp:65-286, pose_estimator.cpp:908-994."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from rpg_monocular_pose_estimator_amd import synth
-from util import p3p_test_problems, check_p3p_solutions, quartic_test_problems, check_quartic_roots
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rpg_monocular_pose_estimator_amd", "csrc")
+from host_builds import build_geom_host
+from util import p3p_test_problems, check_p3p_solutions, quartic_test_problems, check_quartic_roots, unstable_quartic_problems
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp("geom_host")
-    import rpg_monocular_pose_estimator_amd as mpe
-    hip = mpe.device_source()
-    i = hip.index("struct T34 {")
-    with open(os.path.join(d, "k3_extract.inc"), "w") as fh:
-        fh.write(hip[i:hip.index("#define K3_GROUP", i)])
-    i = hip.index("// lexicographic unranking of the idx-th 3-combination")
-    with open(os.path.join(d, "k2_extract.inc"), "w") as fh:
-        fh.write(hip[i:hip.index("#define K2_THREADS", i)])
-        i = hip.index("__device__ __forceinline__ void perm_from_index(")
-        fh.write(hip[i:hip.index("// one entry of the table (layout above) -> e", i)])
-    so = os.path.join(d, "libgeom_host.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", *os.environ.get("MPE_HOST_CXXFLAGS", "").split(), "-I", str(d),
-                           "-I", os.path.join(ROOT, "tests", "host", "stub"), "-I", CSRC,
-                           os.path.join(ROOT, "tests", "host", "geom_host.cpp"), "-o", so])
-    return C.CDLL(so)
+    return build_geom_host(tmp_path_factory.mktemp("geom_host"))
 
 
 @pytest.fixture(scope="module")
@@ -55,20 +36,8 @@ def test_glibc_powers_put_the_quartic_on_the_oracles_digits(host, orc):
     (Ferrari's unstable corner) — its roots are BIT-EQUAL to the oracle's except where glibc misrounds a primitive
     (< 0.3 %), while the arithmetic of rounds 1 - 5 (exact products, cbrt(hypot)) differs in the last digits on a
     third of them and beyond 1e-9 on ~2 %."""
-    rng = np.random.default_rng(3)
-    n = 20000
-    f = np.zeros((n, 5))
-    for i in range(n):
-        m = i % 4
-        if m == 0:
-            f[i] = rng.normal(size=5)
-            continue
-        r = rng.uniform(-1, 1, 4)
-        if m >= 2:
-            r[1] = r[0] + rng.normal() * 10 ** rng.uniform(-9, -3)
-        if m == 3:
-            r[3] = r[2] + rng.normal() * 10 ** rng.uniform(-8, -2)
-        f[i] = np.poly(r) * rng.uniform(0.5, 2)
+    f = unstable_quartic_problems()
+    n = len(f)
     ref = np.array([orc.solve_quartic(f[i]) for i in range(n)])
     res = {}
     for variant in (0, 2):

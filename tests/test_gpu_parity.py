@@ -646,10 +646,10 @@ def test_p3p_batch_matches_oracle(hip, orc):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("variant", [0, 1, 2])
 def test_solve_quartic_batch_matches_oracle(hip, orc, variant):
     """Device quartic (0 = IEEE operators as in the validation / strict voting kernels, 1 = the fast voting
-    kernel's variant) against the oracle.  Every quartic whose real parts differ by more than 1e-9 is counted,
+    kernel's variant, 2 = the powers as libstdc++ / glibc evaluate them: "vote_arith" 3 / 4) against the oracle.  Every quartic whose real parts differ by more than 1e-9 is counted,
     bounded, and must sit in the unstable corner: |alpha + 2y| small against its operands (error amplification
     of the 2 beta / w term ~ 1 / |w|^2), computed here in plain Python complex arithmetic."""
     f, roots = quartic_test_problems(variant)

@@ -109,6 +109,25 @@ def quartic_test_problems(variant):
     return f, roots
 
 
+def unstable_quartic_problems(n=20000):
+    """Random quartics in four equal classes: generic, four real roots, one and two pairs of nearly coinciding roots
+    (Ferrari's unstable corner, where the last digits of the three complex powers pick the branch of the cube root)."""
+    rng = np.random.default_rng(3)
+    f = np.zeros((n, 5))
+    for i in range(n):
+        m = i % 4
+        if m == 0:
+            f[i] = rng.normal(size=5)
+            continue
+        r = rng.uniform(-1, 1, 4)
+        if m >= 2:
+            r[1] = r[0] + rng.normal() * 10 ** rng.uniform(-9, -3)
+        if m == 3:
+            r[3] = r[2] + rng.normal() * 10 ** rng.uniform(-8, -2)
+        f[i] = np.poly(r) * rng.uniform(0.5, 2)
+    return f
+
+
 def check_quartic_roots(got, f, roots, orc):
     """Every quartic whose real parts differ from the oracle's by more than 1e-9 is counted, bounded, and must sit in
     the unstable corner: |alpha + 2y| small against its operands (error amplification of the 2 beta / w term
