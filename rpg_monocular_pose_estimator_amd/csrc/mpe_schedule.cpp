@@ -131,8 +131,9 @@ int make_geom(const mpe_handle* h, int rows, int cols, FrameGeom& g) {
   const size_t per_slot = (size_t)(3 * g.wb + g.tw) * 8 + (size_t)g.wb / 8 + 1;
   size_t fixed = 2 * (size_t)g.rw * 8 + 2 * (size_t)g.rw * 4 + 64;
   long cap = ((long)h->lds_budget - (long)fixed) / (long)per_slot;
+  if (cap < 8) return -1;  // (the BUDGET holds fewer than 8 bitmap rows of this width; asked before the clamp below: a frame
+                           //  of 1 .. 3 rows needs fewer than 8 and was refused with any budget)
   if (cap > rows + 2 + rows / 2) cap = rows + 2 + rows / 2;  // every row active, worst-case separators
-  if (cap < 8) return -1;
   g.slot_cap = (int)cap;
   return 0;
 }

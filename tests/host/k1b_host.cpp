@@ -120,6 +120,12 @@ extern "C" int host_find_leds(const uint8_t* img, int rows, int cols, int thr, c
   return n;
 }
 
+// lds_set_range — how the front phase marks the rows within +-r of a bright segment in its row bitset (s_rowact, 64 words:
+// a bit per row of a frame of up to 4 096 rows) — over n inclusive ranges lohi[2 i] .. lohi[2 i + 1], each shorter than 64.
+extern "C" void host_set_row_ranges(u64* bits, const int* lohi, int n) {
+  for (int i = 0; i < n; ++i) lds_set_range(bits, lohi[2 * i], lohi[2 * i + 1]);
+}
+
 // The image scan's per-segment tests (k1a_scan and the voting kernel's scan rider): bit 0 = any_gt16, bit 1 = maybe_gt16
 extern "C" int host_scan_tests(const uint8_t* seg16, int thr) {
   uint4 v;

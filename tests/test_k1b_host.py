@@ -491,3 +491,166 @@ def test_distortion_models_on_the_host(host, orc):
             kw = dict(dpc.OPEN) if it % 2 else {}
             n_blobs += _same_as_oracle(host, orc, img, kw, K, D, (11, 3) if it < 2 else (0, 0), (name, it))
     assert n_blobs >= 7 * 4 * 6, n_blobs
+
+
+# ---- frames at the frame-size capacity, 4096 x 4000 (frame_size_cases.py) -------------------------------------------------
+# What this tier reaches of the capacity: the literal whole-frame scan (host_find_leds: scan_window over all rows by one
+# lane, which IS k1b_general's fallback for more than 768 bands), the band and (band, column run) decompositions with
+# bitmap rows of 64 words and 4 096 rows, and lds_set_range on all 64 words of the row bitset.  What it does not reach,
+# because it is wave code that could only be restated here, not compiled: the lanes-per-row grouping (lw = 6) of
+# k1b_general's column occupancy, its band list (prefix sums over 64 lanes, the 768-entry cap), the front phase's band
+# builder and its s_colocc words.  Those are the GPU tier's (tests/test_frame_size_capacity.py).
+
+def _touch_bands(mask):
+    """k1b_general's bands, in numpy: maximal runs of non-empty rows in which every row has a pixel 8-adjacent to one of
+    the row above."""
+    m = np.asarray(mask, bool)
+    act = m.any(axis=1)
+    up = np.zeros_like(m)
+    up[1:] = m[:-1]
+    near = up.copy()
+    near[:, 1:] |= up[:, :-1]
+    near[:, :-1] |= up[:, 1:]
+    linked = (m & near).any(axis=1)
+    return int((act & ~linked).sum())
+
+
+def test_capacity_geometry_is_what_the_shapes_are_named_for():
+    """wb, lw, rw and the pitch of every shape of frame_size_cases.py from make_geom's formulas, and the budget
+    arithmetic the refusal tests rely on — numbers only, no device code."""
+    import frame_size_cases as fsc
+    g = {s: fsc.geom(*s) for s in fsc.NARROW + [fsc.FULL]}
+    assert g[17, 4000]["wb"] == 64 and g[17, 4000]["lw"] == 6 and g[17, 4000]["pitch"] == 4000
+    assert g[17, 3999]["wb"] == 64 and g[17, 3999]["pitch"] == 4000 != 3999
+    assert g[17, 3967]["wb"] == 64 and g[17, 3966]["wb"] == 63
+    assert (g[17, 1983]["wb"], g[17, 1983]["lw"]) == (33, 6) and (g[17, 1982]["wb"], g[17, 1982]["lw"]) == (32, 5)
+    assert g[4096, 33]["rw"] == 64 and g[4095, 33]["rw"] == 64 and g[4096, 33]["pitch"] == 48
+    assert g[1537, 33]["rw"] == 25 and g[1600, 48]["pitch"] == 48
+    assert g[fsc.FULL]["wb"] == 64 and g[fsc.FULL]["rw"] == 64 and g[fsc.FULL]["segs_per_row"] == 250
+    # no frame make_geom accepts has a bitmap row of more than 64 words (the g.wb > 64 branch of k1b_general)
+    assert max(fsc.geom(1, c)["wb"] for c in range(1, fsc.MAX_COLS + 1)) == 64 and fsc.geom(1, 4031)["wb"] == 65
+    assert fsc.slot_cap(17, 4000, 8192) == 5 < 8 <= fsc.slot_cap(17, 752, 8192) and fsc.slot_cap(17, 4000) >= 8
+    assert fsc.slot_cap(*fsc.FULL) >= 8
+
+
+def test_capacity_frames_hold_what_the_tests_need(orc):
+    """The requirements on the drawn frames, against the oracle's blurred mask and detections, so that a later edit cannot
+    empty the tests: spots whose mask touches the last row and the last column, masks across x = 1023/1024, 2047/2048,
+    3071/3072 and y = 63/64, 4031/4032, detections on the far side of each, at most 64 of them with and without the
+    salt, and the salt only in the far quarter."""
+    import frame_size_cases as fsc
+    for rows, cols in fsc.NARROW:
+        K, D = synth.camera_for(rows, cols)
+        plain, salted = fsc.frame(rows, cols), fsc.frame(rows, cols, True)
+        _, mask = orc.blur_mask(plain["img"], 140, 0.6)
+        mask = mask > 0
+        assert mask[rows - 1].any() and mask[:, cols - 1].any() and mask[rows - 1, cols - 1], (rows, cols)
+        for x in (1024, 2048, 3072):
+            if x + 25 < cols:
+                assert (mask[:, x - 1] & mask[:, x]).any(), (rows, cols, x)
+        for y in (64, 4032):
+            if y + 9 < rows:
+                assert (mask[y - 1] & mask[y]).any(), (rows, cols, y)
+        und, dist = orc.find_leds(plain["img"], orc.make_params(), K, D)
+        und_s, dist_s = orc.find_leds(salted["img"], orc.make_params(), K, D)
+        assert 4 <= len(dist) <= 64 and dist_s.tobytes() == dist.tobytes(), (rows, cols, len(dist), len(dist_s))
+        assert dist[:, 0].max() > cols - 8 and dist[:, 1].max() > rows - 8, (rows, cols)
+        diff = np.argwhere(plain["img"] != salted["img"])
+        assert len(diff) == salted["n_salt"] > 30 and diff[:, 0].min() >= rows / 2 and diff[:, 1].min() >= cols / 2
+
+
+def test_capacity_shapes_on_the_host(host, orc):
+    """The device blob source over every narrow shape, plain and with the far-quarter salt: the oracle's detections,
+    byte for byte; one shape again behind a ROI origin beyond (2048, 1200)."""
+    import frame_size_cases as fsc
+    n = 0
+    for rows, cols in fsc.NARROW:
+        K, D = synth.camera_for(rows, cols)
+        for clutter in (False, True):
+            n += _same_as_oracle(host, orc, fsc.frame(rows, cols, clutter)["img"], {}, K, D, (0, 0), (rows, cols, clutter))
+    K, D = synth.camera_for(1300, 4100)
+    n += _same_as_oracle(host, orc, fsc.frame(17, 1983, True)["img"], {}, K, D, (2051, 1203), "origin")
+    assert n >= 21 * 5, n
+    # windows of 1, 2 and 3 rows (the last rows of a strip, a one-column window of a column shape): the blur mirrors a
+    # one-row window onto itself; with the filter wide open every contour counts
+    kw = dict(min_blob_area=0.0, max_blob_area=1e9, max_width_height_distortion=1e9, max_circular_distortion=1e9)
+    m = 0
+    for img in (fsc.frame(17, 4000, True)["img"], fsc.frame(17, 1982)["img"]):
+        K, D = synth.camera_for(*img.shape)
+        for h in (1, 2, 3):
+            m += _same_as_oracle(host, orc, np.ascontiguousarray(img[17 - h:]), {}, K, D, (0, 17 - h), h)
+            P = orc.make_params(**kw)
+            ref_und, ref_dist = orc.find_leds(img, P, K, D, roi=(0, 17 - h, img.shape[1], h))
+            und, dist = _host_find_leds(host, orc, np.ascontiguousarray(img[17 - h:]), P, K, D, (0, 17 - h))
+            assert np.array_equal(dist, ref_dist, equal_nan=True) and np.array_equal(und, ref_und, equal_nan=True), h
+            m += len(dist)
+    col = fsc.frame(4096, 33)["img"]
+    m += _same_as_oracle(host, orc, np.ascontiguousarray(col[:, 32:]), kw, *synth.camera_for(4096, 33), (32, 0), "column")
+    assert m >= 20, m
+
+
+def test_capacity_row_bitset_on_the_host(host):
+    """lds_set_range, as the front phase calls it for every bright segment (rows y - r .. y + r, clipped), on frames of
+    4 096 and 4 095 rows: the 64 words against numpy's dilation of the rows that hold a pixel above the threshold; words
+    32 .. 63 (the 1 200-row frames of the other tests end in word 18) all hold a bit."""
+    import frame_size_cases as fsc
+    for rows, cols in ((4096, 33), (4095, 33), (17, 4000)):
+        for r in (1, 2, 4):
+            img = fsc.frame(rows, cols, True)["img"]
+            ys = np.nonzero((img > 140).any(axis=1))[0]
+            lohi = np.ascontiguousarray(np.stack([np.maximum(0, ys - r), np.minimum(rows - 1, ys + r)], 1), np.int32)
+            bits = np.zeros(64, np.uint64)
+            host.host_set_row_ranges(bits.ctypes.data_as(C.c_void_p), lohi.ctypes.data_as(C.c_void_p), len(lohi))
+            want = np.zeros(4096, bool)
+            for lo, hi in lohi:
+                want[lo:hi + 1] = True
+            got = np.unpackbits(bits.view(np.uint8), bitorder="little").astype(bool)
+            assert np.array_equal(got, want), (rows, cols, r)
+            if rows >= 4095:
+                assert bits[32:].all(), (rows, r)     # the salt: a bit in every word of the rows from 2 048 on
+                assert got[rows - 1] and not got[rows:].any()
+
+
+def test_capacity_bands_and_column_runs_on_the_host(host, orc):
+    """scan_window per band and per (band, column run) — the decompositions of k1b_general, called as the kernel calls
+    them — against the whole-frame scan on the blurred masks of 17 x 4000 (bitmap rows of 64 words: the kernel's limit),
+    17 x 3999, 4096 x 33 and 4095 x 33, plain, salted, and the band frames; the band count is numpy's."""
+    import frame_size_cases as fsc
+    host.host_bands_vs_whole.restype = C.c_int
+    host.host_runs_vs_whole.restype = C.c_int
+    shape = np.array([10.0, 200.0, 0.5, 0.5])
+    cases = [(fsc.frame(r, c, s)["img"], 0.6, 0) for r, c in ((17, 4000), (17, 3999), (4096, 33), (4095, 33)) for s in (False, True)]
+    for r, c, sigma, ns in ((4096, 33, fsc.BAND_SIGMA, 6), (4095, 33, fsc.BAND_SIGMA, 6), (1537, 33, fsc.TIGHT_SIGMA, 0),
+                            (1600, 48, fsc.TIGHT_SIGMA, 2), (1536, 33, fsc.TIGHT_SIGMA, 0)):
+        b = fsc.band_frame(r, c, sigma, ns)
+        cases.append((b["img"], sigma, b["n_bands"]))
+    for img, sigma, at_least in cases:
+        rows, cols = img.shape
+        _, mask = orc.blur_mask(img, 140, sigma)
+        mask = np.ascontiguousarray(mask > 0, np.uint8)
+        want = _touch_bands(mask)
+        assert want >= fsc.count_bands(mask) >= at_least, (rows, cols, want, at_least)
+        nb, nr = C.c_int(0), C.c_int(0)
+        rb = host.host_bands_vs_whole(mask.ctypes.data_as(C.c_void_p), rows, cols, shape.ctypes.data_as(C.c_void_p), C.byref(nb))
+        rr = host.host_runs_vs_whole(mask.ctypes.data_as(C.c_void_p), rows, cols, shape.ctypes.data_as(C.c_void_p), C.byref(nr))
+        assert rb >= 1 and rr == rb and nb.value == want and nr.value >= want, (rows, cols, sigma, rb, rr, nb.value, nr.value, want)
+
+
+def test_band_frames_guarantee_their_band_count(host, orc):
+    """The band frames: more than 768 bands (K1B_GEN_BANDS: the whole-frame fallback of k1b_general) on 4096 x 33,
+    4095 x 33 (sigma 0.3, a lone pixel every 4 rows) and on 1537 x 33, 1600 x 48 (sigma 0.2, every 2 rows: no frame of
+    fewer rows can hold that many), exactly 768 on the 1536-row control — counted from how the frame was drawn and
+    confirmed on the oracle's mask; the oracle drops every lone pixel and keeps the spots; the device source's
+    whole-frame scan gives the oracle's bytes."""
+    import frame_size_cases as fsc
+    for rows, cols, sigma, ns, over in ((4096, 33, fsc.BAND_SIGMA, 6, True), (4095, 33, fsc.BAND_SIGMA, 6, True),
+                                        (1537, 33, fsc.TIGHT_SIGMA, 0, True), (1600, 48, fsc.TIGHT_SIGMA, 2, True),
+                                        (1536, 33, fsc.TIGHT_SIGMA, 0, False), (1536, 33, fsc.BAND_SIGMA, 6, False)):
+        b = fsc.band_frame(rows, cols, sigma, ns)
+        _, mask = orc.blur_mask(b["img"], 140, sigma)
+        n_mask = fsc.count_bands(mask > 0)
+        assert (b["n_bands"] > fsc.GEN_BANDS) == over and n_mask >= b["n_bands"], (rows, cols, sigma, b["n_bands"], n_mask)
+        assert over or n_mask <= fsc.GEN_BANDS, (rows, n_mask)
+        K, D = synth.camera_for(rows, cols)
+        n = _same_as_oracle(host, orc, b["img"], dict(gaussian_sigma=sigma), K, D, (0, 0), (rows, cols, sigma))
+        assert n == ns, (rows, cols, sigma, n)
