@@ -911,7 +911,8 @@ typedef struct mpe_rig_init_options {
 } mpe_rig_init_options;
 void mpe_rig_init_default_options(mpe_rig_init_options* o);
 typedef struct mpe_rig_init_info {
-  int reason;                   /* 0 pose; 1 .. 4 as mpe_rig_track_info; 5 ambiguous; 6 no finite hypothesis */
+  int reason;                   /* 0 pose; 1 .. 4 as mpe_rig_track_info; 5 ambiguous; 6 no finite hypothesis;
+                                   7 (mpe_rig_init_bodies_batch only) the body was not asked for */
   int camera;                   /* the winner: its camera (-1 without a winner), */
   int detection[3], marker[3];  /*  detection triple (0-based within the camera's list) and marker triple, */
   int root;                     /*  and root */
@@ -940,6 +941,77 @@ int mpe_rig_init_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_camer
  * none, and refuses what mpe_rig_fuse_trackers refuses. */
 int mpe_rig_init_trackers(mpe_tracker* const* trackers, int n, const double* T_cam_rig, const mpe_rig_init_options* options,
                           mpe_result* rig_out, uint32_t* match_out, mpe_rig_init_info* info_out);
+
+/* ---- several bodies in one frame: rounds of the rig initialiser, each in what the earlier ones left ----
+ * Every other entry assumes ONE body in view.  Here a problem is still one time step of one rig of 1 ..
+ * MPE_RIG_MAX_CAMERAS cameras, with the detection lists and the two tolerance arrays laid out as mpe_rig_init_batch's,
+ * but instead of one marker set there are n_bodies bodies, 1 .. MPE_MAX_BODIES; body b has its own markers and its own
+ * options, and two bodies may have the same marker set.
+ *  claimed_in (optional): one byte per point of det_xy, same indexing; non-zero: the detection is available to no body.
+ *  find (optional): n_problems x n_bodies flags, problem-major; NULL: every body is searched.
+ *  Rounds b = 0 .. n_bodies - 1, in this order, per problem.  The FREE LIST of camera c is its detections that are not
+ *   claimed — by claimed_in or by an earlier round —, in ascending index order.
+ *  find[i][b] == 0: the record has status MPE_FRAME_NO_POSE, T = I, cov = 0 and zero counts, the info record is zeroed
+ *   with reason 7 (not asked), the match words are 0, nothing is claimed.
+ *  Otherwise the record, the info and the match words of (i, b) are what mpe_rig_init_batch returns for the free lists
+ *   with body b's markers and options, byte for byte, except for the indices that name detections: the match words are
+ *   1-based indices within the CALLER's list of that camera and info.detection[3] is 0-based within the caller's list of
+ *   that camera.  info.n_items is the count over the free lists.
+ *  Claim.  When the record has a pose (reason 0), every detection a non-zero match word of this round names is claimed by
+ *   b.  A round without a pose claims nothing.
+ *  owner_out (optional): one int8_t per point of det_xy: -1 free, -2 claimed at entry, else the body that claimed it.
+ * Layouts: out and info_out n_problems x n_bodies records, problem-major; match_out per (problem, body) n_cameras x
+ * MPE_MAX_MARKERS words (a fixed stride, the bodies differ in marker count; the words behind a body's n_markers are 0).
+ * A problem's records do not depend on the rest of the batch.
+ * The acceptance rule is the rig initialiser's above, which is this library's own; for several bodies the reference has
+ * no counterpart at all (its PoseEstimator is one body: initialise() sums the votes of all hypotheses into one histogram,
+ * and two bodies in view vote into the same rows).
+ * The bodies' defaults (options == NULL; mpe_rig_init_bodies_default_options): max_rounds 2; min_margin 0 — an identical
+ * second body always contradicts the winner with equal rows, so the margin test cannot be kept —; with one camera
+ * min_rows = min_markers = n_markers (a single camera can never reach 6 rows of 5 markers), with two or more min_rows 6
+ * and min_markers 4 as mpe_rig_init_default_options.  INTEGRATION.md says what they were checked on.
+ * One submission per call whatever n_bodies is: one input copy, per round the peel step (the claims of the round before,
+ * the free lists compacted on the device) and the initialiser's four launches, one copy back, one synchronise; no host
+ * round trip between rounds.  get "rig_init_bodies_submits" counts the submissions; "rig_init_submits" does not move.
+ * Refusals, all before any device work: those of mpe_rig_init_batch, per body; n_bodies outside 1 .. MPE_MAX_BODIES:
+ * MPE_ERR_ARG; a body that is asked for whose item count over the lists left by claimed_in exceeds 2^22:
+ * MPE_ERR_UNSUPPORTED (later rounds only shrink the lists); a submission of the handle not collected yet.  n_problems == 0
+ * returns MPE_OK. */
+#define MPE_MAX_BODIES 16
+typedef struct mpe_rig_body {
+  const double* markers_xyz;
+  int n_markers;
+  const mpe_rig_init_options* options; /* NULL: the bodies' defaults */
+} mpe_rig_body;
+void mpe_rig_init_bodies_default_options(mpe_rig_init_options* o, int n_cameras, int n_markers);
+int mpe_rig_init_bodies_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const mpe_rig_body* bodies,
+                              int n_bodies, const int* det_begin, const double* det_xy, const uint8_t* claimed_in,
+                              const uint8_t* find, const double* vote_tolerance, const double* accept_tolerance,
+                              int n_problems, mpe_result* out, uint32_t* match_out, mpe_rig_init_info* info_out,
+                              int8_t* owner_out);
+
+/* After a lock-step call over n_bodies x n_cameras trackers, body-major (tracker [b][c] = trackers[b * n_cameras + c] is
+ * body b in camera c; all on one handle): ONE problem through mpe_rig_init_bodies_batch for the bodies with find[b] != 0
+ * (find NULL: all).  Camera c's list is the image points of tracker [b0][c], b0 the lowest body that is asked for — the
+ * points mpe_rig_init_trackers takes; the note on mpe_rig_track_trackers about the whole-image retry applies: a tracker
+ * that was not tracking detects in the whole image, one that lost its body in its ROI brings the ROI's points when the
+ * retry found none.  That tracker's back_projection_pixel_tolerance is the vote and the accept tolerance; body b's
+ * markers are its trackers'; every body runs with the bodies' defaults.  For n_cameras == 1 T_cam_rig may be NULL: the
+ * identity.
+ * Claims at entry come from the bodies that are being tracked: for every [b][c] with find[b] == 0 and updated[b *
+ * n_cameras + c] != 0 (updated NULL: all), each image point a correspondence row of that tracker names claims every
+ * point q of camera c's list with dx * dx + dy * dy <= claim_radius_px^2 (host, plain double).  The radius is there
+ * because a tracked body's points come from the detection in its ROI and the list from a whole-image detection, whose
+ * blobs may differ in the last digits; 0 claims exact coordinates only.
+ * rig_out / info_out: n_bodies records; match_out: n_bodies x n_cameras x MPE_MAX_MARKERS words; owner_out (optional): a
+ * byte per point of the lists, camera after camera.  Tracker state is not touched: seed the found bodies with
+ * mpe_rig_seed_trackers.  Returns the number of bodies that got a pose (find all zero: 0 = MPE_OK, nothing submitted,
+ * every record "not asked"), or < 0: what mpe_rig_fuse_trackers refuses, per body; n_bodies outside 1 ..
+ * MPE_MAX_BODIES; trackers of one camera that differ in K or in the distortion coefficients; a negative or non-finite radius; what the batch entry
+ * refuses. */
+int mpe_rig_init_bodies_trackers(mpe_tracker* const* trackers, int n_bodies, int n_cameras, const double* T_cam_rig,
+                                 const int* find, const int* updated, double claim_radius_px, mpe_result* rig_out,
+                                 uint32_t* match_out, mpe_rig_init_info* info_out, int8_t* owner_out);
 
 /* ---- calibrating the extrinsics of a rig from the body it tracks (a bundle adjustment on the device) ----
  * A recorded sequence of ONE body in front of the rig: view f (a time step) holds the rows [view_begin[f],

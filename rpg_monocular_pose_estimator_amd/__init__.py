@@ -18,7 +18,7 @@ from .binding import (MpeError, MpeParams, MpeResult, MpeDetections, RESULT_DTYP
                       MpeBodyCalibrationOptions, MpeBodyCalibrationReport,
                       MpeRigCalibrationOptions, MpeRigCalibrationReport,
                       MpeRigTrackOptions, MpeRigTrackInfo, RIG_TRACK_INFO_DTYPE,
-                      MpeRigInitOptions, MpeRigInitInfo, RIG_INIT_INFO_DTYPE)
+                      MpeRigInitOptions, MpeRigInitInfo, RIG_INIT_INFO_DTYPE, MpeRigBody, MAX_BODIES, Bodies)
 from .pose_estimator import PoseEstimator  # noqa: F401
 
 __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE", "DETECTIONS_DTYPE",
@@ -33,4 +33,4 @@ __all__ = ["MpeError", "MpeParams", "MpeResult", "MpeDetections", "RESULT_DTYPE"
            "rig_calibration_start", "MpeRigCalibrationOptions", "BodyCalibrator", "pack_body_views",
            "MpeBodyCalibrationOptions", "MpeBodyCalibrationReport",
            "MpeRigCalibrationReport", "MpeRigTrackOptions", "MpeRigTrackInfo", "RIG_TRACK_INFO_DTYPE",
-           "MpeRigInitOptions", "MpeRigInitInfo", "RIG_INIT_INFO_DTYPE"]
+           "MpeRigInitOptions", "MpeRigInitInfo", "RIG_INIT_INFO_DTYPE", "MpeRigBody", "MAX_BODIES", "Bodies"]

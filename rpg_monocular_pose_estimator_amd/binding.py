@@ -90,6 +90,13 @@ RIG_INIT_INFO_DTYPE = np.dtype([("reason", "i4"), ("camera", "i4"), ("detection"
 assert RIG_INIT_INFO_DTYPE.itemsize == C.sizeof(MpeRigInitInfo) == 224
 
 
+class MpeRigBody(C.Structure):  # mpe_rig_body
+    _fields_ = [("markers_xyz", C.POINTER(C.c_double)), ("n_markers", C.c_int), ("options", C.POINTER(MpeRigInitOptions))]
+
+
+MAX_BODIES = 16  # MPE_MAX_BODIES
+
+
 class MpeRigCalibrationOptions(C.Structure):  # mpe_rig_calibration_options
     _fields_ = [("reference_camera", C.c_int), ("max_iterations", C.c_int), ("step_tolerance", C.c_double)]
 
@@ -168,7 +175,7 @@ def source_fingerprint():
                                   "mpe_options.cpp", "mpe_track_abi.cpp", "mpe_abi.cpp", "mpe_track_device.hip",
                                   "mpe_gather.h", "mpe_pixel.h", "mpe_brute_blocks.h", "mpe_wide_peel.h", "mpe_wide.cpp",
                                   "mpe_wide_nn.h", "mpe_rig_gn.h", "mpe_rig_track.h", "mpe_rig_init.h", "mpe_rig.cpp", "mpe_rig_ba.h", "mpe_rig_ba_dev.h",
-                                  "mpe_rig_ba_plan.h", "mpe_body_ba.h", "mpe_body_ba_dev.h", "mpe_body_ba_plan.h"):
+                                  "mpe_rig_peel.h", "mpe_rig_peel.hip", "mpe_rig_ba_plan.h", "mpe_body_ba.h", "mpe_body_ba_dev.h", "mpe_body_ba_plan.h"):
         with open(os.path.join(_CSRC, name), "rb") as fh:
             hsh.update(fh.read())
     return hsh.hexdigest()[:16]
@@ -327,6 +334,14 @@ def load_library():
     lib.mpe_rig_init_trackers.argtypes = [hp, C.c_int, dp, C.POINTER(MpeRigInitOptions), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mpe_rig_track_trackers.argtypes = [hp, C.c_int, dp, dp, C.POINTER(MpeRigTrackOptions), C.c_void_p, C.c_void_p,
                                            C.c_void_p]
+    # several bodies in one frame: rounds of the rig initialiser
+    lib.mpe_rig_init_bodies_default_options.argtypes = [C.POINTER(MpeRigInitOptions), C.c_int, C.c_int]
+    lib.mpe_rig_init_bodies_default_options.restype = None
+    lib.mpe_rig_init_bodies_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MpeRigBody), C.c_int, ip, dp,
+                                              C.c_void_p, C.c_void_p, dp, dp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+    lib.mpe_rig_init_bodies_trackers.argtypes = [hp, C.c_int, C.c_int, dp, ip, ip, C.c_double, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
     # the extrinsics of a rig calibrated from the body it tracks
     lib.mpe_rig_calibration_default_options.argtypes = [C.POINTER(MpeRigCalibrationOptions)]
     lib.mpe_rig_calibration_default_options.restype = None
@@ -1123,6 +1138,44 @@ class Handle:
         self._check(rc, "mpe_rig_init_batch")
         return rec, match, info
 
+    def rig_init_bodies_batch(self, cameras, bodies, detections, vote_tol, accept_tol, claimed=None, find=None):
+        """mpe_rig_init_bodies_batch: several bodies found in one frame, body after body, each in the detections the
+        earlier ones left; one device submission.  cameras, detections, vote_tol / accept_tol as rig_init_batch takes
+        them; bodies: a list of marker sets (n_mk x 3) or of (markers, options) with options a dict over the bodies'
+        defaults (max_rounds, min_rows, min_markers, min_margin) or None; claimed (optional): per problem, per camera a
+        flag per detection (non-zero: available to no body); find (optional): (n, n_bodies) flags.
+        -> (records [RESULT_DTYPE] (n, n_bodies), match (n, n_bodies, n_cam, MAX_MARKERS) uint32, info
+        [RIG_INIT_INFO_DTYPE] (n, n_bodies), owner: per problem, per camera an int8 per detection: -1 free, -2 claimed
+        at entry, else the body)."""
+        n_cam, n, n_b = len(cameras), len(detections), len(bodies)
+        cams = pack_rig_cameras(cameras)
+        packed, keep = pack_rig_bodies(self._lib, bodies, n_cam)
+        lists = [_f64(d).reshape(-1, 2) for dets in detections for d in dets]
+        assert len(lists) == n * n_cam
+        begin = np.zeros(n * n_cam + 1, np.int32)
+        begin[1:] = np.cumsum([len(d) for d in lists])
+        xy = _f64(np.concatenate(lists) if lists else np.zeros((0, 2))).reshape(-1, 2)
+        cl = None
+        if claimed is not None:
+            flags = [np.asarray(f).reshape(-1) != 0 for fl in claimed for f in fl]
+            assert [len(f) for f in flags] == [len(d) for d in lists]
+            cl = np.ascontiguousarray(np.concatenate(flags) if flags else np.zeros(0), np.uint8)
+        fi = None if find is None else np.ascontiguousarray(np.asarray(find).reshape(n, n_b) != 0, np.uint8)
+        tv = _f64(np.broadcast_to(_f64(vote_tol), (n_cam,)))
+        ta = _f64(np.broadcast_to(_f64(accept_tol), (n_cam,)))
+        rec = np.zeros((n, n_b), RESULT_DTYPE)
+        match = np.zeros((n, n_b, n_cam, MAX_MARKERS), np.uint32)
+        info = np.zeros((n, n_b), RIG_INIT_INFO_DTYPE)
+        owner = np.full(len(xy), -1, np.int8)
+        rc = self._lib.mpe_rig_init_bodies_batch(self._h, cams, n_cam, packed, n_b, begin.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 _dp(xy), None if cl is None else cl.ctypes.data,
+                                                 None if fi is None else fi.ctypes.data, _dp(tv), _dp(ta), n,
+                                                 rec.ctypes.data, match.ctypes.data, info.ctypes.data, owner.ctypes.data)
+        del keep
+        self._check(rc, "mpe_rig_init_bodies_batch")
+        own = [[owner[begin[i * n_cam + c]:begin[i * n_cam + c + 1]].copy() for c in range(n_cam)] for i in range(n)]
+        return rec, match, info, own
+
     def rig_calibrate(self, cameras, views, T_views, reference_camera=0, max_iterations=50, step_tolerance=1e-10):
         """mpe_rig_calibrate: the extrinsics of a rig from a recorded sequence of ONE body (a bundle adjustment on the
         device over the extrinsics of all cameras but reference_camera and one pose per view).  cameras: a list of
@@ -1680,6 +1733,95 @@ class Rig:
         return rec, info, upd, rig, fused
 
 
+class Bodies:
+    """Several bodies in front of one rig (or one camera): trackers[b][c] is body b in camera c, all on one handle;
+    T_cam_rig (n_cam, 4, 4), camera <- rig, None for a single camera (the identity).  A tracker's own initialiser sums the
+    votes of everything in view into one histogram and mixes the bodies up, so here a body gets its FIRST pose only from
+    mpe_rig_init_bodies_trackers, which finds body after body, each in the detections the others left; a pose that a
+    tracker's own brute force gave is dropped (the tracker is reset) and the body is searched for with the others'
+    points claimed.  Once seeded, a body's trackers follow it in their ROIs as ever."""
+
+    def __init__(self, handle, trackers, T_cam_rig=None):
+        self.handle = handle
+        self.trackers = [list(ts) for ts in trackers]
+        self.n_bodies, self.n_cam = len(self.trackers), len(self.trackers[0])
+        assert all(len(ts) == self.n_cam for ts in self.trackers)
+        self.T_cam_rig = None if T_cam_rig is None else _f64(T_cam_rig).reshape(self.n_cam, 16)
+        assert self.T_cam_rig is not None or self.n_cam == 1
+        self._flat = [t for ts in self.trackers for t in ts]
+        self._ts = (C.c_void_p * len(self._flat))(*[t._t for t in self._flat])
+        self._rigs = [Rig(handle, ts, np.eye(4).reshape(1, 16) if self.T_cam_rig is None else self.T_cam_rig)
+                      for ts in self.trackers]
+        self.last_init = None  # (records, match, info, owner) of the step's mpe_rig_init_bodies_trackers, or None
+
+    def init(self, find, updated, claim_radius=2.0):
+        """mpe_rig_init_bodies_trackers over the trackers' last frames -> (bodies found, records [RESULT_DTYPE]
+        (n_bodies), match (n_bodies, n_cam, MAX_MARKERS) uint32, info [RIG_INIT_INFO_DTYPE] (n_bodies), owner: per camera
+        an int8 per point of its list — the image points of the first searched body's tracker of that camera)."""
+        lib, nb, nc = self.handle._lib, self.n_bodies, self.n_cam
+        fi = np.ascontiguousarray(np.asarray(find).reshape(nb) != 0, np.int32)
+        up = np.ascontiguousarray(np.asarray(updated).reshape(nb * nc) != 0, np.int32)
+        rec = np.zeros(nb, RESULT_DTYPE)
+        match = np.zeros((nb, nc, MAX_MARKERS), np.uint32)
+        info = np.zeros(nb, RIG_INIT_INFO_DTYPE)
+        lens = [0] * nc
+        if fi.any():
+            b0 = int(np.argmax(fi))
+            lens = [len(self.trackers[b0][c].image_points()) for c in range(nc)]
+        owner = np.full(max(1, sum(lens)), -1, np.int8)
+        ip = C.POINTER(C.c_int)
+        rc = lib.mpe_rig_init_bodies_trackers(self._ts, nb, nc, None if self.T_cam_rig is None else _dp(self.T_cam_rig),
+                                              fi.ctypes.data_as(ip), up.ctypes.data_as(ip), float(claim_radius),
+                                              rec.ctypes.data, match.ctypes.data, info.ctypes.data, owner.ctypes.data)
+        if rc < 0:
+            raise MpeError("mpe_rig_init_bodies_trackers failed (%d): %s" % (rc, lib.mpe_last_error(self.handle._h).decode()))
+        cuts = np.concatenate([[0], np.cumsum(lens)]).astype(int)
+        return rc, rec, match, info, [owner[cuts[c]:cuts[c + 1]].copy() for c in range(nc)]
+
+    def step(self, imgs, times, formats=None, claim_radius=2.0):
+        """One time step: imgs[c] / times[c] camera c's frame and stamp (formats: as tracker_estimate_batch_formats takes
+        them, per camera).  Every body's tracker of camera c gets camera c's image in ONE lock-step call; a body that no
+        camera updated while tracking is searched for with the points of the tracked bodies claimed within
+        claim_radius pixels, and the found ones are seeded.  self.last_init: what that search returned, or None.
+        -> (records [RESULT_DTYPE] (n_bodies): a tracked body's is its tracker's (one camera) or the fusion of its
+        cameras', a searched body's is the search's —, info (n_bodies, n_cam, 8) the lock-step entry's, owner: the
+        search's owner map per camera, or None)."""
+        nb, nc = self.n_bodies, self.n_cam
+        flat_imgs = [imgs[c] for _ in range(nb) for c in range(nc)]
+        flat_times = [float(_f64(times).reshape(-1)[c]) for _ in range(nb) for c in range(nc)]
+        same = formats is None and not _is_torch(imgs[0]) and len({(np.shape(im), np.asarray(im).strides[0]) for im in imgs}) == 1
+        if same:
+            rec, info, upd = tracker_estimate_batch_mixed(self._flat, flat_imgs, flat_times)
+        else:
+            fm = None if formats is None else [formats[c] for _ in range(nb) for c in range(nc)]
+            rec, info, upd = tracker_estimate_batch_formats(self._flat, flat_imgs, flat_times, fm)
+        rec, info = rec.reshape(nb, nc), info.reshape(nb, nc, 8)
+        # a camera counts when its tracker followed the body; what its own brute force found may be any body's
+        tracked = np.asarray(upd, bool).reshape(nb, nc) & (info[:, :, 7] == 0)
+        find = ~tracked.any(axis=1)
+        out = np.zeros(nb, RESULT_DTYPE)
+        t = float(np.max(_f64(times)))
+        for b in range(nb):
+            if find[b]:
+                continue
+            if nc == 1:
+                out[b] = rec[b, 0]
+            else:
+                out[b] = self._rigs[b].fuse(tracked[b])[1][0]
+        self.last_init, owner = None, None
+        if find.any():
+            _, found, match, iinfo, owner = self.init(find, tracked, claim_radius)
+            self.last_init = (found, match, iinfo, owner)
+            for b in np.nonzero(find)[0]:
+                out[b] = found[b]
+                if found[b]["status"] == 0:
+                    self._rigs[b].seed(np.ones(nc, np.int32), found[b]["T"], t)
+                else:
+                    for tr in self.trackers[b]:
+                        tr.reset()
+        return out, info, owner
+
+
 def pack_rig_cameras(cameras):
     """[(K 3x3, T_cam_rig 4x4)] -> mpe_rig_camera array"""
     cams = (MpeRigCamera * max(1, len(cameras)))()
@@ -1709,6 +1851,34 @@ def rig_init_options(lib, options):
             raise TypeError("unknown option %r" % k)
         setattr(opt, k, int(v))
     return opt
+
+
+def rig_init_bodies_options(lib, options, n_cameras, n_markers):
+    """max_rounds / min_rows / min_markers / min_margin over the bodies' defaults -> MpeRigInitOptions"""
+    opt = MpeRigInitOptions()
+    lib.mpe_rig_init_bodies_default_options(C.byref(opt), int(n_cameras), int(n_markers))
+    for k, v in (options or {}).items():
+        if k not in ("max_rounds", "min_rows", "min_markers", "min_margin"):
+            raise TypeError("unknown option %r" % k)
+        setattr(opt, k, int(v))
+    return opt
+
+
+def pack_rig_bodies(lib, bodies, n_cameras):
+    """[markers (n_mk x 3) | (markers, options dict or None)] -> (mpe_rig_body array, what it points to: keep it alive)"""
+    arr = (MpeRigBody * max(1, len(bodies)))()
+    keep = []
+    for a, body in zip(arr, bodies):
+        markers, options = body if isinstance(body, tuple) else (body, None)
+        mk = _f64(markers).reshape(-1, 3)
+        a.markers_xyz = mk.ctypes.data_as(C.POINTER(C.c_double))
+        a.n_markers = len(mk)
+        keep.append(mk)
+        if options is not None:
+            opt = rig_init_bodies_options(lib, options, n_cameras, len(mk))
+            a.options = C.pointer(opt)
+            keep.append(opt)
+    return arr, keep
 
 
 def pack_rig_views(cameras, views):

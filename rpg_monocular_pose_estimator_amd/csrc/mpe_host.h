@@ -119,6 +119,8 @@ struct mpe_handle {
   long long bruteforce_submits = 0;
   // get "rig_init_submits": device submissions of mpe_rig_init_batch (one per call with a problem in it)
   long long rig_init_submits = 0;
+  // get "rig_init_bodies_submits": device submissions of mpe_rig_init_bodies_batch (one per call, whatever n_bodies is)
+  long long rig_init_bodies_submits = 0;
   // the *_wide entries (mpe_wide.cpp): get "wide_frames" — detection sets mpe_solve_bruteforce_batch_wide has solved;
   // option "wide_block_cap" (tests): blocks per set of the wide voting launch at most, 0 = four per compute unit
   long long wide_frames = 0;

@@ -235,6 +235,31 @@ struct RigInitDev {
   mpe_rig_init_info* info;
 };
 hipError_t launch_k_rig_init(const RigInitDev& d, hipStream_t s);
+// The step in front of round `round` of mpe_rig_init_bodies_batch (mpe_rig_peel.hip; logic in mpe_rig_peel.h):
+// k_rig_peel_count, and for round < n_bodies k_rig_peel_scan and k_rig_peel_scatter, in this order on s.  The caller's
+// lists: det_begin (n_problems * n_cam + 1, from 0, each list at most MPE_MAX_DETECTIONS points: the caller checks),
+// det_xy, owner_in (a byte per point: -1 free, -2 claimed at entry), find (n_problems * n_bodies bytes).  The round's
+// lists, written here: counts, r_begin (+ 1), r_xy and map (as many as det_xy has points).  r_out / r_match / r_info: what
+// round - 1 (a body of n_mk_prev markers) answered, in launch_k_rig_init's layout; out / match / info / owner: the call's
+// answer, (problem, body) records, match n_cam * MPE_MAX_MARKERS words each.  Everything in device memory.
+enum { MPE_RIG_PEEL_LANES = 64, MPE_RIG_PEEL_SCAN_LANES = 256 };
+struct RigPeelDev {
+  const int* det_begin;
+  const double* det_xy;
+  const int8_t* owner_in;
+  const uint8_t* find;
+  int n_cam, n_problems, n_bodies;
+  int *counts, *r_begin, *map;
+  double* r_xy;
+  const mpe_result* r_out;
+  const uint32_t* r_match;
+  const mpe_rig_init_info* r_info;
+  int8_t* owner;
+  mpe_result* out;
+  uint32_t* match;
+  mpe_rig_init_info* info;
+};
+hipError_t launch_k_rig_peel(const RigPeelDev& d, int round, int n_mk_prev, hipStream_t s);
 // the steps of mpe_rig_calibrate (mpe_rig_ba.h), each a launch of its own: linearise / update over the used views
 // [first, first + count) of one chunk, reduce over the same with flag = 1 when the sums start anew, finish with flag = 1
 // when the cameras take their step; solve and covariance take neither.  The table holds device pointers.

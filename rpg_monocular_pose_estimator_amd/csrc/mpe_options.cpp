@@ -287,6 +287,7 @@ int mpe_get_option(mpe_handle* h, const char* name, int* value) {
   else if (n == "track_batch_reruns") *value = (int)h->track_batch_reruns;
   else if (n == "bruteforce_submits") *value = (int)h->bruteforce_submits;
   else if (n == "rig_init_submits") *value = (int)h->rig_init_submits;
+  else if (n == "rig_init_bodies_submits") *value = (int)h->rig_init_bodies_submits;
   else if (n == "wide_frames") *value = (int)h->wide_frames;
   else if (n == "wide_track_submits") *value = (int)h->wide_track_submits;
   else if (n == "wide_block_cap") *value = h->wide_block_cap;

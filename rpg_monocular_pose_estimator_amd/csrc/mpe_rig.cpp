@@ -3,7 +3,9 @@
 // rows that bring their own camera: one input copy, one launch, one copy back.  mpe_rig_track_batch — the partial-view
 // tracking step (k_rig_track; logic in mpe_rig_track.h), submitted the same way.  mpe_rig_init_batch — the body found
 // with the whole rig (k_rig_init_vote / _winner / _finish; logic in mpe_rig_init.h): the host counts the items and the
-// voting blocks of every problem, one input copy, four launches, one copy back.  What works on the trackers of a rig
+// voting blocks of every problem, one input copy, four launches, one copy back.  mpe_rig_init_bodies_batch — several bodies
+// in one frame: that chain once per body over the detections the earlier bodies left, the peel step of mpe_rig_peel.hip
+// (logic in mpe_rig_peel.h) between the rounds, still one input copy and one copy back.  What works on the trackers of a rig
 // (mpe_rig_fuse_trackers, mpe_rig_track_trackers, mpe_rig_init_trackers, mpe_rig_seed_trackers) is in mpe_tracker.cpp, beside the state it reads and sets, and comes
 // here through the public entry.  mpe_rig_calibrate — the extrinsics of a rig from a recorded sequence of the body: which
 // rows take part and the iteration are mpe_rig_ba_plan.h (shared with the CPU tier), the steps are the k_rig_ba_* kernels
@@ -412,6 +414,199 @@ int mpe_rig_init_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_camer
   std::memcpy(out, mb + back_off, rec_bytes);
   if (match_out) std::memcpy(match_out, mb + back_off + m_off, match_words * sizeof(uint32_t));
   if (info_out) std::memcpy(info_out, mb + back_off + i_off, (size_t)n_problems * sizeof(mpe_rig_init_info));
+  return MPE_OK;
+}
+
+void mpe_rig_init_bodies_default_options(mpe_rig_init_options* o, int n_cameras, int n_markers) {
+  if (!o) return;
+  mpe_rig_init_default_options(o);
+  o->min_margin = 0;  // (an identical second body always contradicts the winner with equal rows)
+  if (n_cameras <= 1) o->min_rows = o->min_markers = n_markers;
+}
+
+int mpe_rig_init_bodies_batch(mpe_handle* h, const mpe_rig_camera* cameras, int n_cameras, const mpe_rig_body* bodies,
+                              int n_bodies, const int* det_begin, const double* det_xy, const uint8_t* claimed_in,
+                              const uint8_t* find, const double* vote_tolerance, const double* accept_tolerance,
+                              int n_problems, mpe_result* out, uint32_t* match_out, mpe_rig_init_info* info_out,
+                              int8_t* owner_out) {
+  // (the handle is looked at behind everything that can be refused without it)
+  if (n_problems < 0) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (!cameras) return fail(h, MPE_ERR_ARG, "cameras is null");
+  if (!bodies) return fail(h, MPE_ERR_ARG, "bodies is null");
+  if (!det_begin) return fail(h, MPE_ERR_ARG, "det_begin is null");
+  if (!vote_tolerance || !accept_tolerance) return fail(h, MPE_ERR_ARG, "a tolerance array is null");
+  if (!out) return fail(h, MPE_ERR_ARG, "out is null");
+  if (n_cameras < 1 || n_cameras > MPE_RIG_MAX_CAMERAS) return fail(h, MPE_ERR_ARG, "n_cameras outside 1 .. MPE_RIG_MAX_CAMERAS");
+  if (n_bodies < 1 || n_bodies > MPE_MAX_BODIES) return fail(h, MPE_ERR_ARG, "n_bodies outside 1 .. MPE_MAX_BODIES");
+  std::vector<mpe_rig_init_options> opts((size_t)n_bodies);
+  for (int b = 0; b < n_bodies; ++b) {
+    if (!bodies[b].markers_xyz) return fail(h, MPE_ERR_ARG, "markers_xyz of a body is null");
+    if (bodies[b].n_markers < 1 || bodies[b].n_markers > MPE_MAX_MARKERS) return fail(h, MPE_ERR_ARG, "n_markers of a body outside 1 .. MPE_MAX_MARKERS");
+    mpe_rig_init_options& opt = opts[(size_t)b];
+    mpe_rig_init_bodies_default_options(&opt, n_cameras, bodies[b].n_markers);
+    if (bodies[b].options) opt = *bodies[b].options;
+    if (opt.max_rounds < 1 || opt.max_rounds > 4) return fail(h, MPE_ERR_ARG, "max_rounds outside 1 .. 4");
+    if (opt.min_rows < 3) return fail(h, MPE_ERR_ARG, "min_rows must be >= 3");
+    if (opt.min_markers < 1) return fail(h, MPE_ERR_ARG, "min_markers must be >= 1");
+    if (opt.min_margin < 0) return fail(h, MPE_ERR_ARG, "min_margin must be >= 0");
+  }
+  for (int c = 0; c < n_cameras; ++c)
+    if (!(vote_tolerance[c] > 0) || !(accept_tolerance[c] > 0)) return fail(h, MPE_ERR_ARG, "a tolerance is not > 0");
+  if (n_problems == 0) return MPE_OK;
+  const size_t n_lists = (size_t)n_problems * (size_t)n_cameras;
+  if (det_begin[0] < 0) return fail(h, MPE_ERR_ARG, "det_begin is negative");
+  for (size_t i = 0; i < n_lists; ++i)
+    if (det_begin[i + 1] < det_begin[i]) return fail(h, MPE_ERR_ARG, "det_begin decreases");
+  for (size_t i = 0; i < n_lists; ++i)
+    if (det_begin[i + 1] - det_begin[i] > MPE_MAX_DETECTIONS)
+      return fail(h, MPE_ERR_UNSUPPORTED, "more than MPE_MAX_DETECTIONS detections in a camera's list");
+  const int d0 = det_begin[0], n_det = det_begin[n_lists] - d0;
+  if (n_det > 0 && !det_xy) return fail(h, MPE_ERR_ARG, "det_xy is null");
+  // what claimed_in leaves of every list
+  std::vector<int> n_left(n_lists);
+  for (size_t l = 0; l < n_lists; ++l) {
+    int n = 0;
+    for (int k = det_begin[l]; k < det_begin[l + 1]; ++k) n += (!claimed_in || claimed_in[k] == 0) ? 1 : 0;
+    n_left[l] = n;
+  }
+  // The voting blocks of every round, counted ONCE per body from the lists claimed_in leaves: an upper bound for the
+  // round itself, whose lists the earlier rounds have only shortened.  The kernels allow that as they are:
+  // k_rig_init_vote takes its item count from the lists it staged (S.off[n_cam]), a block beyond that count writes
+  // rig_init_no_key() / runner 0, and k_rig_init_winner / _finish reduce over whatever blocks there are — the keys are
+  // totally ordered, so the surplus blocks do not show.  A body that is not asked for in a problem gets no block there.
+  std::vector<int> chunk_begin((size_t)n_bodies * ((size_t)n_problems + 1), 0);
+  int max_chunks = 0;
+  for (int b = 0; b < n_bodies; ++b) {
+    const long long nm = bodies[b].n_markers;
+    const long long perms = nm >= 3 ? nm * (nm - 1) * (nm - 2) : 0;
+    int* cb = chunk_begin.data() + (size_t)b * ((size_t)n_problems + 1);
+    for (int i = 0; i < n_problems; ++i) {
+      long long items = 0;
+      if (!find || find[(size_t)i * n_bodies + b] != 0)
+        for (int c = 0; c < n_cameras; ++c) {
+          const long long n = n_left[(size_t)i * n_cameras + c];
+          if (n >= 3) items += n * (n - 1) * (n - 2) / 6 * perms;
+        }
+      if (items > MPE_RIG_INIT_ITEM_CAP) return fail(h, MPE_ERR_UNSUPPORTED, "more than 2^22 items (detection triples x marker permutations) for a body in a problem");
+      const long long blocks = (items + MPE_RIG_INIT_BLOCK_ITEMS - 1) / MPE_RIG_INIT_BLOCK_ITEMS;
+      if (cb[i] + blocks > 0x7fffffffLL) return fail(h, MPE_ERR_UNSUPPORTED, "more than 2^31 voting blocks in a round");
+      cb[i + 1] = cb[i] + (int)blocks;
+    }
+    max_chunks = cb[n_problems] > max_chunks ? cb[n_problems] : max_chunks;
+  }
+  if (!h) return fail(h, MPE_ERR_ARG, "bad argument");
+  if (h->pending_track_n || h->submit_seq != h->collect_seq)
+    return fail(h, MPE_ERR_ARG, "a submitted batch has not been collected yet");
+  ENTER(h);
+  // in: [cameras | vote tolerances | accept tolerances | det_begin (rebased to 0) | detections | owner bytes at entry |
+  // find | per body: markers, chunk_begin]; back: [records | match words | info records | owner bytes]; on the device
+  // only: the rounds' [keys | winners | runners | winner row sets], the round's lists [counts | det_begin | index map |
+  // detections] and the round's answer [records | match words | info records]
+  const size_t n_rec = (size_t)n_problems * (size_t)n_bodies;
+  const size_t cam_bytes = (size_t)n_cameras * sizeof(mpe_rig_camera);
+  const size_t tv_off = up256(cam_bytes);
+  const size_t ta_off = tv_off + up256((size_t)n_cameras * sizeof(double));
+  const size_t beg_off = ta_off + up256((size_t)n_cameras * sizeof(double));
+  const size_t det_off = beg_off + up256((n_lists + 1) * sizeof(int));
+  const size_t own_off = det_off + up256((size_t)n_det * 2 * sizeof(double));
+  const size_t find_off = own_off + up256((size_t)n_det);
+  const size_t body_off = find_off + up256(n_rec);
+  const size_t mk_bytes = up256((size_t)MPE_MAX_MARKERS * 3 * sizeof(double));
+  const size_t body_bytes = mk_bytes + up256(((size_t)n_problems + 1) * sizeof(int));
+  const size_t in_bytes = body_off + (size_t)n_bodies * body_bytes;
+  const size_t rec_bytes = n_rec * sizeof(mpe_result);
+  const size_t match_words = n_rec * (size_t)n_cameras * MPE_MAX_MARKERS;
+  const size_t m_off = up256(rec_bytes);
+  const size_t i_off = m_off + up256(match_words * sizeof(uint32_t));
+  const size_t o_off = i_off + up256(n_rec * sizeof(mpe_rig_init_info));
+  const size_t back_bytes = o_off + up256((size_t)n_det);
+  const size_t back_off = up256(in_bytes);
+  const size_t win_off = up256((size_t)max_chunks * MPE_RIG_INIT_KEY_BYTES);
+  const size_t run_off = win_off + up256((size_t)n_problems * MPE_RIG_INIT_KEY_BYTES);
+  const size_t rows_off = run_off + up256((size_t)max_chunks * sizeof(int));
+  const size_t cnt_off = rows_off + up256((size_t)n_problems * MPE_RIG_MAX_CAMERAS * MPE_MAX_MARKERS);
+  const size_t rbeg_off = cnt_off + up256(n_lists * sizeof(int));
+  const size_t map_off = rbeg_off + up256((n_lists + 1) * sizeof(int));
+  const size_t rxy_off = map_off + up256((size_t)n_det * sizeof(int));
+  const size_t rrec_off = rxy_off + up256((size_t)n_det * 2 * sizeof(double));
+  const size_t rm_off = rrec_off + up256((size_t)n_problems * sizeof(mpe_result));
+  const size_t ri_off = rm_off + up256(n_lists * MPE_MAX_MARKERS * sizeof(uint32_t));
+  const size_t work_bytes = ri_off + up256((size_t)n_problems * sizeof(mpe_rig_init_info));
+  { const int rc = grow_mailbox(h, back_off + back_bytes); if (rc != MPE_OK) return rc; }
+  uint8_t* mb = static_cast<uint8_t*>(h->mailbox);
+  std::memcpy(mb, cameras, cam_bytes);
+  std::memcpy(mb + tv_off, vote_tolerance, (size_t)n_cameras * sizeof(double));
+  std::memcpy(mb + ta_off, accept_tolerance, (size_t)n_cameras * sizeof(double));
+  int* hb = reinterpret_cast<int*>(mb + beg_off);
+  for (size_t i = 0; i <= n_lists; ++i) hb[i] = det_begin[i] - d0;
+  if (n_det > 0) std::memcpy(mb + det_off, det_xy + (size_t)2 * d0, (size_t)n_det * 2 * sizeof(double));
+  for (int k = 0; k < n_det; ++k) reinterpret_cast<int8_t*>(mb + own_off)[k] = (claimed_in && claimed_in[d0 + k] != 0) ? -2 : -1;
+  for (size_t k = 0; k < n_rec; ++k) mb[find_off + k] = (!find || find[k] != 0) ? 1 : 0;
+  for (int b = 0; b < n_bodies; ++b) {
+    uint8_t* p = mb + body_off + (size_t)b * body_bytes;
+    std::memcpy(p, bodies[b].markers_xyz, (size_t)bodies[b].n_markers * 3 * sizeof(double));
+    std::memcpy(p + mk_bytes, chunk_begin.data() + (size_t)b * ((size_t)n_problems + 1), ((size_t)n_problems + 1) * sizeof(int));
+  }
+  HIP_TRY(h, h->frames.reserve(in_bytes));
+  HIP_TRY(h, h->results.reserve(back_bytes));
+  HIP_TRY(h, h->scratch.reserve(work_bytes));
+  uint8_t* d_in = static_cast<uint8_t*>(h->frames.p);
+  uint8_t* d_back = static_cast<uint8_t*>(h->results.p);
+  uint8_t* d_work = static_cast<uint8_t*>(h->scratch.p);
+  HIP_TRY(h, hipMemcpyAsync(d_in, mb, in_bytes, hipMemcpyHostToDevice, h->stream));
+  RigPeelDev p;
+  p.det_begin = reinterpret_cast<const int*>(d_in + beg_off);
+  p.det_xy = reinterpret_cast<const double*>(d_in + det_off);
+  p.owner_in = reinterpret_cast<const int8_t*>(d_in + own_off);
+  p.find = d_in + find_off;
+  p.n_cam = n_cameras, p.n_problems = n_problems, p.n_bodies = n_bodies;
+  p.counts = reinterpret_cast<int*>(d_work + cnt_off);
+  p.r_begin = reinterpret_cast<int*>(d_work + rbeg_off);
+  p.map = reinterpret_cast<int*>(d_work + map_off);
+  p.r_xy = reinterpret_cast<double*>(d_work + rxy_off);
+  mpe_result* r_out = reinterpret_cast<mpe_result*>(d_work + rrec_off);
+  uint32_t* r_match = reinterpret_cast<uint32_t*>(d_work + rm_off);
+  mpe_rig_init_info* r_info = reinterpret_cast<mpe_rig_init_info*>(d_work + ri_off);
+  p.r_out = r_out, p.r_match = r_match, p.r_info = r_info;
+  p.out = reinterpret_cast<mpe_result*>(d_back);
+  p.match = reinterpret_cast<uint32_t*>(d_back + m_off);
+  p.info = reinterpret_cast<mpe_rig_init_info*>(d_back + i_off);
+  p.owner = reinterpret_cast<int8_t*>(d_back + o_off);
+  RigLaunchTimer timer(h);
+  HIP_TRY(h, timer.begin());
+  for (int b = 0; b <= n_bodies; ++b) {
+    // the claims and the answer of round b - 1, then (b < n_bodies) the lists of round b
+    HIP_TRY(h, launch_k_rig_peel(p, b, b > 0 ? bodies[b - 1].n_markers : 0, h->stream));
+    if (b == n_bodies) break;
+    const uint8_t* body = d_in + body_off + (size_t)b * body_bytes;
+    RigInitDev d;
+    d.cams = reinterpret_cast<const mpe_rig_camera*>(d_in);
+    d.markers = reinterpret_cast<const double*>(body);
+    d.det_xy = p.r_xy;
+    d.tol_vote = reinterpret_cast<const double*>(d_in + tv_off);
+    d.tol_accept = reinterpret_cast<const double*>(d_in + ta_off);
+    d.det_begin = p.r_begin;
+    d.chunk_begin = reinterpret_cast<const int*>(body + mk_bytes);
+    d.n_cam = n_cameras, d.n_markers = bodies[b].n_markers, d.n_problems = n_problems;
+    d.n_chunks = chunk_begin[(size_t)b * ((size_t)n_problems + 1) + (size_t)n_problems];
+    const mpe_rig_init_options& opt = opts[(size_t)b];
+    d.max_rounds = opt.max_rounds, d.min_rows = opt.min_rows, d.min_markers = opt.min_markers, d.min_margin = opt.min_margin;
+    d.keys = reinterpret_cast<RigInitKey*>(d_work);
+    d.winner = reinterpret_cast<RigInitKey*>(d_work + win_off);
+    d.runners = reinterpret_cast<int*>(d_work + run_off);
+    d.win_rows = d_work + rows_off;
+    d.out = r_out, d.match = r_match, d.info = r_info;
+    HIP_TRY(h, launch_k_rig_init(d, h->stream));
+  }
+  HIP_TRY(h, timer.end());
+  ++h->rig_init_bodies_submits;
+  HIP_TRY(h, hipMemcpyAsync(mb + back_off, d_back, back_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  timer.read();
+  std::memcpy(out, mb + back_off, rec_bytes);
+  if (match_out) std::memcpy(match_out, mb + back_off + m_off, match_words * sizeof(uint32_t));
+  if (info_out) std::memcpy(info_out, mb + back_off + i_off, n_rec * sizeof(mpe_rig_init_info));
+  if (owner_out && n_det > 0) std::memcpy(owner_out + d0, mb + back_off + o_off, (size_t)n_det);
   return MPE_OK;
 }
 

@@ -591,6 +591,112 @@ int mpe_rig_init_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig
   return rig_out->status == MPE_FRAME_POSE ? 1 : 0;
 }
 
+int mpe_rig_init_bodies_trackers(mpe_tracker* const* ts, int n_bodies, int n_cameras, const double* T_cam_rig, const int* find,
+                                 const int* updated, double claim_radius_px, mpe_result* rig_out, uint32_t* match_out,
+                                 mpe_rig_init_info* info_out, int8_t* owner_out) {
+  if (!ts || n_bodies < 1 || n_cameras < 1 || !ts[0]) return MPE_ERR_ARG;
+  mpe_handle* h = ts[0]->h;
+  if (n_bodies > MPE_MAX_BODIES) {
+    mpe_host::set_error(h, "n_bodies outside 1 .. MPE_MAX_BODIES");
+    return MPE_ERR_ARG;
+  }
+  const bool args_ok = (T_cam_rig || n_cameras == 1) && rig_out;
+  for (int b = 0; b < n_bodies; ++b) {
+    if (const int refused = rig_trackers_refused(ts + (size_t)b * n_cameras, n_cameras, args_ok)) return refused;
+    if (ts[(size_t)b * n_cameras]->h != h) {
+      mpe_host::set_error(h, "the trackers of all bodies must be on one handle");
+      return MPE_ERR_ARG;
+    }
+    for (int c = 0; c < n_cameras; ++c) {
+      const mpe_tracker* t = ts[(size_t)b * n_cameras + c];
+      for (size_t k = 0; k < (size_t)b * n_cameras; ++k)
+        if (ts[k] == t) {
+          mpe_host::set_error(h, "a tracker is given twice");
+          return MPE_ERR_ARG;
+        }
+      // (one camera: the claims compare tracker [b][c]'s undistorted points with the list of tracker [b0][c])
+      if (std::memcmp(t->K, ts[c]->K, sizeof(t->K)) != 0 || t->D != ts[c]->D) {
+        mpe_host::set_error(h, "the trackers of one camera must share its K and D");
+        return MPE_ERR_ARG;
+      }
+    }
+  }
+  if (!(claim_radius_px >= 0) || !std::isfinite(claim_radius_px)) {
+    mpe_host::set_error(h, "claim_radius_px must be finite and >= 0");
+    return MPE_ERR_ARG;
+  }
+  int b0 = -1;
+  for (int b = 0; b < n_bodies && b0 < 0; ++b)
+    if (!find || find[b]) b0 = b;
+  if (b0 < 0) {  // nobody is asked for: every record "not asked", nothing submitted
+    for (int b = 0; b < n_bodies; ++b) {
+      std::memset(&rig_out[b], 0, sizeof(mpe_result));
+      for (int i = 0; i < 16; i += 5) rig_out[b].T[i] = 1.0;
+      rig_out[b].status = MPE_FRAME_NO_POSE;
+      if (info_out) {
+        std::memset(&info_out[b], 0, sizeof(mpe_rig_init_info));
+        info_out[b].reason = 7;
+      }
+    }
+    if (match_out) std::memset(match_out, 0, (size_t)n_bodies * n_cameras * MPE_MAX_MARKERS * sizeof(uint32_t));
+    return MPE_OK;
+  }
+  // camera c's list: the image points of the first searched body's tracker of that camera (as mpe_rig_init_trackers takes
+  // them), its back-projection tolerance for the vote and the accept test
+  std::vector<mpe_rig_camera> cams((size_t)n_cameras);
+  std::vector<int> det_begin((size_t)n_cameras + 1, 0);
+  std::vector<double> det_xy, tol((size_t)n_cameras);
+  for (int c = 0; c < n_cameras; ++c) {
+    const mpe_tracker* t = ts[(size_t)b0 * n_cameras + c];
+    std::memcpy(cams[(size_t)c].K, t->K, sizeof(t->K));
+    if (T_cam_rig) {
+      std::memcpy(cams[(size_t)c].T_cam_rig, T_cam_rig + 16 * (size_t)c, 16 * sizeof(double));
+    } else {
+      for (int i = 0; i < 16; ++i) cams[(size_t)c].T_cam_rig[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    }
+    det_xy.insert(det_xy.end(), t->det.begin(), t->det.end());
+    det_begin[(size_t)c + 1] = (int)det_xy.size() / 2;
+    tol[(size_t)c] = t->p.back_projection_pixel_tolerance;
+  }
+  // claims at entry: the points the tracked bodies' correspondence rows name, each with its radius (a tracked body's
+  // points come from its ROI detection, the list from a whole-image one).  Plain double: two products and one sum.
+  std::vector<uint8_t> claimed(det_xy.size() / 2, 0), asked((size_t)n_bodies, 0);
+  const double r2 = claim_radius_px * claim_radius_px;
+  for (int b = 0; b < n_bodies; ++b) {
+    asked[(size_t)b] = (!find || find[b]) ? 1 : 0;
+    if (asked[(size_t)b]) continue;
+    for (int c = 0; c < n_cameras; ++c) {
+      if (updated && !updated[(size_t)b * n_cameras + c]) continue;
+      const mpe_tracker* t = ts[(size_t)b * n_cameras + c];
+      const int n_m = n_markers(t), n_d = (int)t->det.size() / 2;
+      for (size_t r = 0; r + 1 < t->corr.size(); r += 2) {
+        const int m = (int)t->corr[r], d = (int)t->corr[r + 1];
+        if (m < 1 || m > n_m || d < 1 || d > n_d) continue;
+        const double px = t->det[2 * (size_t)(d - 1)], py = t->det[2 * (size_t)(d - 1) + 1];
+        for (int q = det_begin[(size_t)c]; q < det_begin[(size_t)c + 1]; ++q) {
+          const double dx = det_xy[2 * (size_t)q] - px, dy = det_xy[2 * (size_t)q + 1] - py;
+          const double xx = dx * dx, yy = dy * dy;
+          if (xx + yy <= r2) claimed[(size_t)q] = 1;
+        }
+      }
+    }
+  }
+  std::vector<mpe_rig_body> bodies((size_t)n_bodies);
+  for (int b = 0; b < n_bodies; ++b) {
+    const mpe_tracker* t = ts[(size_t)b * n_cameras];
+    bodies[(size_t)b].markers_xyz = t->markers.data();
+    bodies[(size_t)b].n_markers = n_markers(t);
+    bodies[(size_t)b].options = nullptr;
+  }
+  const int rc = mpe_rig_init_bodies_batch(h, cams.data(), n_cameras, bodies.data(), n_bodies, det_begin.data(), det_xy.data(),
+                                           claimed.data(), asked.data(), tol.data(), tol.data(), 1, rig_out, match_out, info_out,
+                                           owner_out);
+  if (rc != MPE_OK) return rc;
+  int found = 0;
+  for (int b = 0; b < n_bodies; ++b) found += rig_out[b].status == MPE_FRAME_POSE ? 1 : 0;
+  return found;
+}
+
 int mpe_rig_seed_trackers(mpe_tracker* const* ts, int n, const double* T_cam_rig, const int* seed, const double rig_pose[16],
                           double time, const double* rig_prev_pose, double prev_time) {
   if (!ts || n < 1 || n > MPE_RIG_MAX_CAMERAS || !T_cam_rig || !seed || !rig_pose) return MPE_ERR_ARG;

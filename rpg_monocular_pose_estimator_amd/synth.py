@@ -240,6 +240,68 @@ def make_sequence(config, n, seed, dt=0.02, lin_speed=0.15, ang_speed=0.6, dropo
     return dict(frames=frames, T_true=np.array(Ts), times=np.arange(n) * dt, K=K, D=D, markers=M, rows=rows, cols=cols)
 
 
+def make_bodies_sequence(config, n, seed, n_bodies, markers=None, min_sep=12.0, dropout=None, only=None, dt=0.02,
+                         lin_speed=0.15, ang_speed=0.6, max_tries=20000):
+    """Several bodies in front of ONE camera, rendered into the same frames: body b moves on a trajectory of its own
+    (make_sequence's model: constant twist + small jitter, frame k at time k*dt, make_sequence's margins), and a set of
+    trajectories is accepted only when the blobs of DIFFERENT bodies are at least min_sep pixels apart in every frame.
+    markers: a list of n_bodies marker sets (default: the config's for every body — identical bodies); dropout: {body:
+    frames in which NONE of its LEDs is rendered}; only: render this body alone (the same poses; the background noise
+    is another draw).  Deterministic in the seed.
+    -> dict(frames (n, rows, cols), T_true (n_bodies, n, 4, 4), spots [per body (n, n_mk, 2) distorted pixels], times, K,
+    D, markers [per body], rows, cols)."""
+    cfg = CONFIGS[config] if isinstance(config, str) else config
+    K, D = camera_for(cfg["rows"], cfg["cols"])
+    rows, cols = cfg["rows"], cfg["cols"]
+    Ms = [np.asarray(cfg["markers"] if markers is None else markers[b], np.float64).reshape(-1, 3) for b in range(n_bodies)]
+    dropout = {} if dropout is None else {int(b): set(int(k) for k in fr) for b, fr in dropout.items()}
+    rng = np.random.default_rng([seed, 23])
+
+    def trajectory(M):
+        T0, _ = sample_scene(rng, M, K, D, rows, cols, 0, margin=80.0)
+        v = rng.normal(size=3)
+        v *= lin_speed / np.linalg.norm(v)
+        w = rng.normal(size=3)
+        w *= ang_speed / np.linalg.norm(w)
+        Ts, px = [], []
+        for k in range(n):
+            t = k * dt
+            Tk = np.eye(4)
+            Tk[:3, :3] = rodrigues(w, np.linalg.norm(w) * t) @ T0[:3, :3]
+            Tk[:3, 3] = T0[:3, 3] + v * t + 0.0005 * rng.normal(size=3)
+            p = distort_px(project(Tk, M, K), K, D)
+            d = np.linalg.norm(p[:, None, :] - p[None, :, :], axis=-1) + np.eye(len(M)) * 1e9
+            if (p[:, 0].min() < 20 or p[:, 0].max() > cols - 21 or p[:, 1].min() < 20 or p[:, 1].max() > rows - 21
+                    or Tk[2, 3] < 0.5 or d.min() < 12.0):
+                return None
+            Ts.append(Tk)
+            px.append(p)
+        return np.array(Ts), np.array(px)
+
+    Ts, px = [], []
+    for _ in range(max_tries):
+        if len(Ts) == n_bodies:
+            break
+        tr = trajectory(Ms[len(Ts)])
+        if tr is None:
+            continue
+        apart = all(np.linalg.norm(tr[1][k][:, None, :] - other[k][None, :, :], axis=-1).min() >= min_sep
+                    for other in px for k in range(n))
+        if apart:
+            Ts.append(tr[0])
+            px.append(tr[1])
+    if len(Ts) < n_bodies:
+        raise ValueError("make_bodies_sequence: no trajectories keep the bodies' blobs min_sep apart")
+    frames = np.empty((n, rows, cols), np.uint8)
+    for k in range(n):
+        shown = [px[b][k] for b in range(n_bodies) if (only is None or b == only) and k not in dropout.get(b, ())]
+        spots = np.concatenate(shown) if shown else np.zeros((0, 2))
+        key = [seed, k, 3] if only is None else [seed, k, 3, 1 + int(only)]
+        frames[k] = render_frame(np.random.default_rng(key), spots, rows, cols, cfg["spot_sigma"])
+    return dict(frames=frames, T_true=np.array(Ts), spots=px, times=np.arange(n) * dt, K=K, D=D, markers=Ms, rows=rows,
+                cols=cols)
+
+
 def make_rig_sequence(config, n, seed, cameras, T_cam_rig, dropout=None, dt=0.02, lin_speed=0.15, ang_speed=0.6,
                       max_tries=20000, visible=None, true_markers=None):
     """One body seen by the cameras of a calibrated rig: ONE smooth trajectory in the rig frame (make_sequence's model:
